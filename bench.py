@@ -16,7 +16,12 @@ reported beside it.
 per GPU, before anything touches a GPU); under torchrun the ranks come from
 RANK / WORLD_SIZE / LOCAL_RANK.
 
-Side legs on the same run: the batched checker (config C3, 100M boards per GPU
+A plain run measures the headline alone: it sets up, warms up, times the steps,
+checks the boards, writes them if `--dump-outputs DIR` is given, and prints the
+line.  Everything below, and the single-context figure with its rooflines,
+runs with `--full`.
+
+Side legs of a `--full` run: the batched checker (config C3, 100M boards per GPU
 by default, HBM-bound), config C2 (1M ~30-clue puzzles per GPU), config C5 (an
 exhaustive count of one 15-clue board, its frontier split over all ranks, the
 count combined by an RCCL all-reduce over xGMI), config C1 (POST /solve latency on
@@ -57,6 +62,16 @@ def parse_args():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: the single-context figure with its per-launch kernel time and "
+                         "rooflines, the checker (C3), the weak-scaling figure (N > 1), every side leg and the CPU "
+                         "baselines.  Without it the run sets up, warms up, times the headline's --steps passes, "
+                         "checks every solved board and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write what the headline's last timed pass returned -- the solved "
+                         "boards (rows x 81) and their statuses -- as DIR/solved.npy and DIR/status.npy (float32; "
+                         "_rank<r> before .npy at N > 1).  Above DUMP_ROWS rows per rank: a fixed sample of that "
+                         "many rows, drawn from --seed")
     ap.add_argument("--inflight", type=int, default=2,
                     help="C4 headline: passes in flight per rank -- consecutive passes issued on this many engine "
                          "contexts in turn (own HIP stream, dequeue state and output buffer each), so one pass's "
@@ -874,7 +889,24 @@ def kernel_clock(e, d_in, d_out, d_st, n, launches=20):
                       "(prop32_clock_kernel, the stamped twin of the timed kernel), median"}
 
 
-def solve_leg(eng, d, args, puzzles, expected, steps, warmup, contexts=1, timed=True, clock=False):
+DUMP_ROWS = 1 << 17               # --dump-outputs: rows per rank (x 82 float32 = 43 MB)
+
+
+def dump_outputs(path, d, args, out, st):
+    """--dump-outputs: one pass's solved boards and statuses (this rank's slice) as float32 .npy
+    files; above DUMP_ROWS rows a sorted sample of DUMP_ROWS of them, the same rows on every run
+    with the same --seed (and rank)."""
+    os.makedirs(path, exist_ok=True)
+    n = len(out)
+    if n > DUMP_ROWS:
+        rows = np.sort(np.random.default_rng([args.seed, d.rank, 0xD0]).choice(n, DUMP_ROWS, replace=False))
+        out, st = out[rows], st[rows]
+    tag = f"_rank{d.rank}" if d.world > 1 else ""
+    np.save(os.path.join(path, f"solved{tag}.npy"), out.astype(np.float32))
+    np.save(os.path.join(path, f"status{tag}.npy"), st.astype(np.float32))
+
+
+def solve_leg(eng, d, args, puzzles, expected, steps, warmup, contexts=1, timed=True, clock=False, dump=""):
     """Time `steps` sdk_solve_batch_dev passes over this rank's resident slice (barrier +
     device sync on both sides, max over ranks); verify every board afterwards.  Each rank's clock
     runs from the release of the opening barrier to its own device sync at the end, and the job's
@@ -934,6 +966,13 @@ def solve_leg(eng, d, args, puzzles, expected, steps, warmup, contexts=1, timed=
                 spans = spans[0::2]
             kernel_ms += sum(spans)
             launches += len(spans)
+    if dump and steps > 0:      # the last timed pass's buffers, before anything else runs
+        out = np.empty((n, 81), np.uint8)
+        st_h = np.empty(n, np.int8)
+        o, st = outs[(steps - 1) % nctx]
+        o.download(out)
+        st.download(st_h)
+        dump_outputs(dump, d, args, out, st_h)
     # the clock the timed passes ran at: more passes of the same kind straight after them (events off)
     solve_leg.clock = kernel_clock(eng, d_in, outs[0][0], outs[0][1], n) if clock else None
     elapsed_max = d.max(elapsed)
@@ -954,6 +993,40 @@ def solve_leg(eng, d, args, puzzles, expected, steps, warmup, contexts=1, timed=
     avg_kernel_s = kernel_ms / 1000.0 / max(launches, 1)
     solve_leg.fallback_ms = sum(fallback) / len(fallback) if fallback else None
     return elapsed_max, avg_kernel_s, bad_total
+
+
+def headline_fields(args, d, total, n, inflight, elapsed_max):
+    """The result line's headline: `steps` timed passes over the whole job took `elapsed_max` s."""
+    return {
+        "metric": METRIC,
+        "value": total * args.steps / elapsed_max,
+        "unit": "puzzles/s",
+        "n_gpus": d.world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": elapsed_max / args.steps * 1000.0,
+        "higher_is_better": True,
+        "scaling": "strong",
+        "vs_baseline": None,
+        "dtype": "u8",
+        "data": "synthetic",
+        "config": {
+            "workload": ("C4: 17-clue hard puzzles (seeds S1-S5 x seeded Sudoku symmetries), "
+                         if args.workload == "solve17" else
+                         "C2: ~30-clue unique puzzles (17 seed givens + 13 solution cells, symmetries), ")
+                        + f"{total} puzzles sharded over {d.world} GPU(s), resident in HBM",
+            "puzzles_total": total,
+            "puzzles_per_gpu": n,
+            "order": args.order,
+            "solver": args.solver,
+            "parallelism": f"batch-shard x{d.world} (contiguous slices, no collectives)",
+            "passes_in_flight_per_gpu": inflight,
+            "warmup_policy": (f"W = {args.warmup} untimed passes, continued back to back until {args.warm_ms:g} ms "
+                              "of load before each timed region (the clock ramps from ~1.9 to ~2.35 GHz over "
+                              "the first ~40 ms; profiles/r06/clock_ramp_r06i.jsonl); exactly `steps` passes "
+                              "timed"),
+        },
+    }
 
 
 def main():
@@ -995,7 +1068,7 @@ def main():
     # Runs before the solver leg, on a fresh allocation: measured after the solver leg the same
     # kernel read ~9% slower on the same box (profiles/r01/check_variants.txt).
     checker_leg = None
-    if args.check_boards > 0:
+    if args.full and args.check_boards > 0:
         nb = args.check_boards
         pool_n = min(nb, 1 << 20)
         pool, pool_exp = synth.make_check_boards(pool_n, seed=args.seed + 7, lo=d.rank * pool_n)
@@ -1056,25 +1129,39 @@ def main():
     gen = synth.make_17clue if args.workload == "solve17" else synth.make_30clue
     puzzles, expected = gen(hi - lo, seed=args.seed, lo=lo)
     n = hi - lo
+    inflight = max(1, args.inflight)
+    if not args.full:
+        # the headline alone: `inflight` passes in flight, every output buffer checked
+        elapsed_max, _, bad_total = solve_leg(eng, d, args, puzzles, expected, args.steps, args.warmup,
+                                              contexts=inflight, timed=False, dump=args.dump_outputs)
+        result = headline_fields(args, d, total, n, inflight, elapsed_max)
+        result["parity"] = {"mismatched_boards": bad_total,
+                            "checked_boards": total * max(1, min(inflight, args.steps))}
+        eng.close()
+        if d.rank == 0:
+            print(json.dumps(result), flush=True)
+        d.close()
+        if bad_total:
+            sys.exit(3)
+        return
     # one context first: its per-launch HIP events are the kernel's own duration (the roofline's
     # denominator); then the headline with `inflight` passes in flight (every pass solves the whole
     # slice, every output buffer is checked)
     s_el, avg_kernel_s, bad_total = solve_leg(eng, d, args, puzzles, expected, args.steps, args.warmup,
-                                              clock=args.solver == "quad" and "prop32" in solve_kernel)
+                                              clock=args.solver == "quad" and "prop32" in solve_kernel,
+                                              dump=args.dump_outputs if inflight == 1 else "")
     single_stream = {"value": total * args.steps / s_el, "unit": "puzzles/s", "ms_per_step": s_el / args.steps * 1e3,
                      "avg_kernel_ms": avg_kernel_s * 1e3, "contexts": 1,
                      "avg_fallback_ms": solve_leg.fallback_ms, "clock": solve_leg.clock,
                      "warm_passes": solve_leg.warm_passes,
                      "parity": {"mismatched_boards": bad_total, "checked_boards": total}}
-    inflight = max(1, args.inflight)
     if inflight > 1:
         elapsed_max, _, bad_if = solve_leg(eng, d, args, puzzles, expected, args.steps, args.warmup,
-                                           contexts=inflight, timed=False)
+                                           contexts=inflight, timed=False, dump=args.dump_outputs)
         bad_total += bad_if
     else:
         elapsed_max = s_el
 
-    value = total * args.steps / elapsed_max
     achieved = SOLVE_BYTES_PER_PUZZLE * n / avg_kernel_s / 1e9
     srec = pmc_record(args.pmc_summary, solve_kernel, n)
     roofline = {
@@ -1166,39 +1253,12 @@ def main():
             "stalls": srec.get("stalls"),
             "source": os.path.relpath(args.pmc_summary, ROOT),
         }
-    result = {
-        "metric": METRIC,
-        "value": value,
-        "unit": "puzzles/s",
-        "n_gpus": d.world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": elapsed_max / args.steps * 1000.0,
-        "higher_is_better": True,
-        "scaling": "strong",
-        "vs_baseline": None,
-        "dtype": "u8",
-        "data": "synthetic",
-        "config": {
-            "workload": ("C4: 17-clue hard puzzles (seeds S1-S5 x seeded Sudoku symmetries), "
-                         if args.workload == "solve17" else
-                         "C2: ~30-clue unique puzzles (17 seed givens + 13 solution cells, symmetries), ")
-                        + f"{total} puzzles sharded over {d.world} GPU(s), resident in HBM",
-            "puzzles_total": total,
-            "puzzles_per_gpu": n,
-            "order": args.order,
-            "solver": args.solver,
-            "parallelism": f"batch-shard x{d.world} (contiguous slices, no collectives)",
-            "passes_in_flight_per_gpu": inflight,
-            "warmup_policy": (f"W = {args.warmup} untimed passes, continued back to back until {args.warm_ms:g} ms "
-                              "of load before each timed region (the clock ramps from ~1.9 to ~2.35 GHz over "
-                              "the first ~40 ms; profiles/r06/clock_ramp_r06i.jsonl); exactly `steps` passes "
-                              "timed"),
-        },
+    result = headline_fields(args, d, total, n, inflight, elapsed_max)
+    result.update({
         "single_stream": single_stream,
         "roofline": roofline,
         "parity": {"mismatched_boards": bad_total, "checked_boards": total * (1 + inflight if inflight > 1 else 1)},
-    }
+    })
 
     # side legs run under a watchdog: if one stalls (e.g. a collective), rank 0
     # still prints the line with everything measured so far

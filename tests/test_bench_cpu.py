@@ -27,7 +27,7 @@ sys.meta_path.insert(0, _NoTorch())
 """
 
 
-def _run_bench(gpus, extra=(), tmp=None):
+def _run_bench(gpus, extra=(), tmp=None, full=True):
     paths = [ROOT, os.path.join(ROOT, "tests")]
     if tmp is not None:
         with open(os.path.join(tmp, "sitecustomize.py"), "w") as f:
@@ -41,6 +41,8 @@ def _run_bench(gpus, extra=(), tmp=None):
            "--first-boards", "",
            "--cpu-seconds", "0",
            "--http-requests", "0", "--pmc-summary", "", "--engine-factory", "doubles:BenchStubEngine", *extra]
+    if full:
+        cmd.append("--full")
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = p.stdout.splitlines()
@@ -67,6 +69,69 @@ def test_bench_gpus1_single_process(tmp_path):
     assert r["n_gpus"] == 1 and "weak_scaling" not in r
     k = r["config"]["passes_in_flight_per_gpu"]
     assert r["parity"] == {"mismatched_boards": 0, "checked_boards": (1 + k) * 301}
+
+
+def test_bench_plain_run_is_the_headline_alone(tmp_path):
+    """Without --full: the headline's fields and its parity, none of the other legs (the checker
+    and the side legs are left at sizes that would run them)."""
+    r = _run_bench(1, extra=["--steps", "3", "--c2-puzzles", "50", "--count-leg", "1"], tmp=tmp_path, full=False)
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert key in r, key
+    assert r["steps"] == 3 and r["ms_per_step"] > 0 and r["unit"] == "puzzles/s"
+    assert abs(r["value"] - 301 / (r["ms_per_step"] / 1000.0)) <= 1e-6 * r["value"]
+    k = r["config"]["passes_in_flight_per_gpu"]
+    assert r["parity"] == {"mismatched_boards": 0, "checked_boards": k * 301}
+    for key in ("checker", "checker_summary", "single_stream", "roofline", "roofline_summary", "c2_30clue",
+                "c5_count", "cpu_baseline", "weak_scaling"):
+        assert key not in r, key
+
+
+def test_bench_dump_outputs_repeats(tmp_path):
+    """--dump-outputs: the last timed pass's boards and statuses as float32 arrays, the same from
+    run to run, with and without --full; they are the batch's expected solutions."""
+    import numpy as np
+    from distributed_sudoku_solver_amd import synth
+    dumps = []
+    for name, full in (("a", False), ("b", False), ("c", True)):
+        out = tmp_path / name
+        r = _run_bench(1, extra=["--dump-outputs", str(out)], tmp=tmp_path, full=full)
+        assert r["parity"]["mismatched_boards"] == 0
+        assert sorted(os.listdir(out)) == ["solved.npy", "status.npy"]
+        dumps.append((np.load(out / "solved.npy"), np.load(out / "status.npy")))
+    solved, status = dumps[0]
+    assert solved.dtype == np.float32 and solved.shape == (301, 81)
+    assert status.dtype == np.float32 and status.shape == (301,) and (status == 1).all()
+    for s2, st2 in dumps[1:]:
+        assert np.array_equal(solved, s2) and np.array_equal(status, st2)
+    _, expected = synth.make_30clue(301, seed=20250614, lo=0)
+    assert np.array_equal(solved, expected.astype(np.float32))
+
+
+def test_dump_outputs_samples_a_large_batch(tmp_path):
+    """Above DUMP_ROWS rows the dump is a fixed sample: the same sorted rows for the same seed,
+    other rows for another seed, at most 64 MB in all."""
+    import importlib.util
+    import types
+    import numpy as np
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    n = bench.DUMP_ROWS + 1001
+    out = (np.arange(n, dtype=np.uint32)[:, None] * 7 + np.arange(81, dtype=np.uint32)[None, :]).astype(np.uint8)
+    st = (out[:, 0] % 3).astype(np.int8) - 1
+    d = types.SimpleNamespace(rank=0, world=1)
+    got = {}
+    for name, seed in (("a", 5), ("b", 5), ("c", 6)):
+        bench.dump_outputs(str(tmp_path / name), d, types.SimpleNamespace(seed=seed), out, st)
+        got[name] = (np.load(tmp_path / name / "solved.npy"), np.load(tmp_path / name / "status.npy"))
+        assert sum(os.path.getsize(tmp_path / name / f) for f in os.listdir(tmp_path / name)) <= 64 * 1000 * 1000
+    a, a_st = got["a"]
+    assert a.shape == (bench.DUMP_ROWS, 81) and a_st.shape == (bench.DUMP_ROWS,) and a.dtype == np.float32
+    assert np.array_equal(a, got["b"][0]) and np.array_equal(a_st, got["b"][1])
+    assert not np.array_equal(a, got["c"][0])
+    # every dumped row is a row of the batch with its own status
+    keys = {r.tobytes(): int(s) for r, s in zip(out[:256], st[:256])}     # the rows repeat every 256
+    assert all(keys[r.astype(np.uint8).tobytes()] == int(s) for r, s in zip(a[:2000], a_st[:2000]))
 
 
 def test_bench_gpus2_count_legs_over_tcp_rccl_stub(tmp_path):

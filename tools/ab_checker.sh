@@ -2,7 +2,7 @@
 # Checker leg alone, in-tree library against build/variants/lib_<v>.so, alternating (dev tool; GPU box).
 # usage: VARIANTS="head" bash tools/ab_checker.sh [reps]   -> per run: library, timed kernel ms, fraction of 8 TB/s
 set -o pipefail
-OFF="--batch 1024 --c2-puzzles 0 --minimal-puzzles 0 --hard-leg 0 --count-leg 0 --lane-puzzles 0 --cpu-seconds 0 --http-requests 0 --first-boards="
+OFF="--full --batch 1024 --c2-puzzles 0 --minimal-puzzles 0 --hard-leg 0 --count-leg 0 --lane-puzzles 0 --cpu-seconds 0 --http-requests 0 --first-boards="
 for rep in $(seq ${1:-3}); do
   for v in intree ${VARIANTS:-}; do
     if [ $v = intree ]; then unset SDK_LIB_PATH; else export SDK_LIB_PATH=$PWD/build/variants/lib_$v.so; fi

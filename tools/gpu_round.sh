@@ -20,32 +20,32 @@ for s in $steps; do
       || { echo "smoke failed"; tail -20 "$out/smoke.log"; exit 1; }
     cat "$out/smoke.log" ;;
   bench)
-    timeout -k 10 420 python -u bench.py > "$out/bench.json" 2> "$out/bench.err" \
+    timeout -k 10 420 python -u bench.py --full > "$out/bench.json" 2> "$out/bench.err" \
       || { echo "bench failed"; tail -20 "$out/bench.err"; exit 1; }
     cat "$out/bench.json" ;;
   prof)
     (cd /tmp && timeout -k 10 420 rocprofv3 --kernel-trace --stats -d "$root/$out/prof" -o run \
-      --output-format csv -- python3 "$root/bench.py" --cpu-seconds 0 --http-requests 0 \
+      --output-format csv -- python3 "$root/bench.py" --full --cpu-seconds 0 --http-requests 0 \
       > "$root/$out/prof_bench.json" 2> "$root/$out/prof.err") \
       || { echo "rocprof failed"; tail -20 "$out/prof.err"; exit 1; }
     find "$out/prof" -name '*kernel_stats.csv' -exec cat {} \; ;;
   prof_c4)   # the headline launch alone: solve4_kernel's average = the C4 launch the bench line times
              # (single stream: --inflight 1, one context, per-launch HIP events)
     (cd /tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$root/$out/prof_c4" -o run \
-      --output-format csv -- python3 "$root/bench.py" --check-boards 0 --c2-puzzles 0 --minimal-puzzles 0 --hard-leg 0 \
+      --output-format csv -- python3 "$root/bench.py" --full --check-boards 0 --c2-puzzles 0 --minimal-puzzles 0 --hard-leg 0 \
       --count-leg 0 --lane-puzzles 0 --cpu-seconds 0 --http-requests 0 --inflight 1 > "$root/$out/prof_c4_bench.json" 2> "$root/$out/prof_c4.err") \
       || { echo "rocprof c4 failed"; tail -20 "$out/prof_c4.err"; exit 1; }
     find "$out/prof_c4" -name '*kernel_stats.csv' -exec cat {} \; ;;
   prof_c3)   # the checker launch alone (C4 shrunk to 1024 puzzles)
     (cd /tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$root/$out/prof_c3" -o run \
-      --output-format csv -- python3 "$root/bench.py" --batch 1024 --c2-puzzles 0 --minimal-puzzles 0 --hard-leg 0 \
+      --output-format csv -- python3 "$root/bench.py" --full --batch 1024 --c2-puzzles 0 --minimal-puzzles 0 --hard-leg 0 \
       --count-leg 0 --lane-puzzles 0 --cpu-seconds 0 --http-requests 0 > "$root/$out/prof_c3_bench.json" 2> "$root/$out/prof_c3.err") \
       || { echo "rocprof c3 failed"; tail -20 "$out/prof_c3.err"; exit 1; }
     find "$out/prof_c3" -name '*kernel_stats.csv' -exec cat {} \; ;;
   pmc)
     for c in FETCH_SIZE WRITE_SIZE; do
       (cd /tmp && timeout -s KILL 240 rocprofv3 --pmc $c --output-format csv -d "$root/$out/pmc_$c" -o run -- \
-        python3 "$root/bench.py" --steps 2 --warmup 0 --check-steps 2 --cpu-seconds 0 --http-requests 0 \
+        python3 "$root/bench.py" --full --steps 2 --warmup 0 --check-steps 2 --cpu-seconds 0 --http-requests 0 \
         > "$root/$out/pmc_$c.json" 2> "$root/$out/pmc_$c.err") \
         || { echo "pmc $c failed"; tail -20 "$out/pmc_$c.err"; exit 1; }
     done

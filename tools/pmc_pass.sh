@@ -5,4 +5,4 @@ set -o pipefail
 out=$1; tag=$2; shift 2
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 timeout -s KILL 150 rocprofv3 --pmc "$@" --output-format csv -d "$out" -o "$tag" -- \
-  python3 bench.py --steps 2 --warmup 0 --check-steps 2 --cpu-seconds 0 --batch 2000000 --check-boards 50000000
+  python3 bench.py --full --steps 2 --warmup 0 --check-steps 2 --cpu-seconds 0 --batch 2000000 --check-boards 50000000

@@ -11,7 +11,7 @@
 set -o pipefail
 out=$1; shift; root=$(pwd); mkdir -p "$out"; export TMPDIR=/tmp
 passes=${*:-cal calw c4 c3 min hard}
-OFF="--c2-puzzles 0 --minimal-puzzles 0 --hard-leg 0 --count-leg 0 --lane-puzzles 0 --cpu-seconds 0 --http-requests 0 --pmc-summary="
+OFF="--full --c2-puzzles 0 --minimal-puzzles 0 --hard-leg 0 --count-leg 0 --lane-puzzles 0 --cpu-seconds 0 --http-requests 0 --pmc-summary="
 C4="$root/bench.py --steps 2 --warmup 1 --check-boards 0 $OFF"
 C3="$root/bench.py --steps 1 --warmup 0 --batch 1024 --check-boards 100000000 --check-steps 2 --check-warmup 1 $OFF"
 MIN="$root/tools/solve_profile.py --workload minimal --n 1048576 --reps 2 --donate 0 --solver quad"

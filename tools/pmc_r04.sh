@@ -11,7 +11,7 @@
 set -o pipefail
 out=$1; shift; root=$(pwd); mkdir -p "$out"; export TMPDIR=/tmp
 passes=${*:-c4 hard1m min}
-OFF="--c2-puzzles 0 --minimal-puzzles 0 --hard-leg 0 --count-leg 0 --lane-puzzles 0 --cpu-seconds 0 --http-requests 0 --pmc-summary="
+OFF="--full --c2-puzzles 0 --minimal-puzzles 0 --hard-leg 0 --count-leg 0 --lane-puzzles 0 --cpu-seconds 0 --http-requests 0 --pmc-summary="
 C4="$root/bench.py --steps 2 --warmup 1 --check-boards 0 $OFF"
 HARD1M="$root/tools/solve_profile.py --workload hard --n 1000000 --reps 2 --donate 0 --solver quad"
 MIN="$root/tools/solve_profile.py --workload minimal --n 1048576 --reps 2 --donate 0 --solver quad"
