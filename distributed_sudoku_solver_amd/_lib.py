@@ -147,6 +147,11 @@ SIGNATURES = {
     "sdk_timer_read": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int64)]),
 }
 
+# diagnostics the library exports beside the header (sudoku_hip.hip, "diagnostics (not in the header)")
+DEBUG_SIGNATURES = {
+    "sdk_debug_p32_list": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)]),
+}
+
 _lib = None
 
 
@@ -168,6 +173,12 @@ def load():
     # entry points; the in-tree library must export every one
     override = "SDK_LIB_PATH" in os.environ
     for name, (res, args) in SIGNATURES.items():
+        if override and not hasattr(lib, name):
+            continue
+        fn = getattr(lib, name)
+        fn.restype = res
+        fn.argtypes = args
+    for name, (res, args) in DEBUG_SIGNATURES.items():
         if override and not hasattr(lib, name):
             continue
         fn = getattr(lib, name)

@@ -1352,7 +1352,7 @@ int sdk_set_option(sdk_ctx* c, int key, int64_t value) {
             c->prop32 = (int)value;
             return SDK_OK;
         case SDK_OPT_PROP32_LC:
-            if ((value & 0xFF) < 1 || (value & 0xFF) > 64 || (value >> 8) > 64)
+            if (value < 0 || (value & 0xFF) < 1 || (value & 0xFF) > 64 || (value >> 8) > 64)
                 return fail(SDK_EINVAL, "SDK_OPT_PROP32_LC: period 1..64 | first step 0..64 << 8");
             c->prop32_lc = (int)value;
             return SDK_OK;
@@ -1431,6 +1431,32 @@ extern "C" int sdk_debug_clock_read(sdk_ctx* c, double* out4, int64_t* workgroup
     out4[2] = ghz[(ghz.size() * 9) / 10];
     out4[3] = sum / (double)ghz.size();
     *workgroups = (int64_t)ghz.size();
+    return SDK_OK;
+}
+
+// diagnostics (not in the header): what the last solve's prop32 pass left to the search.  Waits for
+// that solve on the context's stream; *count = the boards the pass listed (p32_list[0]; 0 when the
+// last solve did not run the pass), and the first min(*count, cap) of them come back in list order
+// (not deterministic: workgroups reserve list slots with an atomic add) -- index[i] the board's
+// index in the batch, grids[81 i ..] what the search was given for it (p32_in: the propagated grid
+// under handover, else the input; the fallback only reads that buffer -- launch_solve takes it as
+// its const input and dn_collect copies from it into dn_in).
+extern "C" int sdk_debug_p32_list(sdk_ctx* c, uint32_t* index, uint8_t* grids, int64_t cap, int64_t* count) {
+    if (!c || !count || cap < 0 || (cap > 0 && (!index || !grids))) return fail(SDK_EINVAL, "NULL argument");
+    std::lock_guard<std::mutex> lk(c->mu);
+    *count = 0;
+    if (!c->prop32_ran || !c->p32_list.p || !c->p32_in.p) return SDK_OK;
+    HIPCALL(hipSetDevice(c->device));
+    uint32_t v = 0;
+    HIPCALL(hipMemcpyAsync(&v, c->p32_list.p, sizeof v, hipMemcpyDeviceToHost, c->stream));
+    HIPCALL(hipStreamSynchronize(c->stream));
+    *count = v;
+    const size_t k = (size_t)std::min<int64_t>((int64_t)v, cap);
+    if (k == 0) return SDK_OK;
+    HIPCALL(hipMemcpyAsync(index, static_cast<const uint32_t*>(c->p32_list.p) + 1, k * 4, hipMemcpyDeviceToHost,
+                           c->stream));
+    HIPCALL(hipMemcpyAsync(grids, c->p32_in.p, k * 81, hipMemcpyDeviceToHost, c->stream));
+    HIPCALL(hipStreamSynchronize(c->stream));
     return SDK_OK;
 }
 

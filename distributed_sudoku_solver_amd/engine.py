@@ -215,6 +215,20 @@ class SudokuEngine:
         L.check(self.lib.sdk_timer_read(self.ctx, ctypes.byref(ms), ctypes.byref(n)), "sdk_timer_read")
         return ms.value, n.value
 
+    def debug_p32_list(self, cap):
+        """What the last solve's propagation pass left to the search (sdk_debug_p32_list, a
+        diagnostic): (count, uint32[k] board indices, uint8[k,81] the grids the search was given),
+        k = min(count, cap), in the pass's list order (not deterministic: sort by index).  count is 0
+        when the last solve did not run the pass."""
+        cap = max(0, int(cap))
+        index = np.zeros(max(cap, 1), dtype=np.uint32)
+        grids = np.zeros((max(cap, 1), 81), dtype=np.uint8)
+        count = ctypes.c_int64()
+        L.check(self.lib.sdk_debug_p32_list(self.ctx, _ptr(index), _ptr(grids), cap, ctypes.byref(count)),
+                "sdk_debug_p32_list")
+        k = min(count.value, cap)
+        return count.value, index[:k].copy(), grids[:k].copy()
+
     def alloc(self, nbytes):
         return DeviceBuffer(self, nbytes)
 

@@ -231,7 +231,7 @@ def test_prop32_lc_schedules_same_answers(engine, lc):
 
 def test_prop32_lc_option_encoding(engine):
     assert engine.get_option(L.SDK_OPT_PROP32_LC) == 5 | (3 << 8)          # the default schedule
-    for bad in (0, 65, 5 | (65 << 8), 3 << 8):
+    for bad in (0, 65, 5 | (65 << 8), 3 << 8, -255, -1):
         with pytest.raises(Exception):
             engine.set_option(L.SDK_OPT_PROP32_LC, bad)
     assert engine.get_option(L.SDK_OPT_PROP32_LC) == 5 | (3 << 8)
