@@ -59,9 +59,9 @@ constexpr uint32_t kP32URec = 72;        // bytes per unit record: (T_d, twos_d)
 constexpr uint32_t kP32TRec = 40;        // bytes per triad record: 9 words + pad
 constexpr uint32_t kP32ColTri = 1280;    // the column triads' records (32 row-triad slots before)
 constexpr uint32_t kP32Region = 3456;    // bytes per half: 81 cell records + the spare lanes' record 81
+                                         // (= 32 boards x 108 B of the answers' staging, p32_stage_byte)
 constexpr uint32_t kP32Table = 2 * kP32Region;   // p32_unit's read order, 40 B per lane (p32_order_table)
 constexpr uint32_t kP32Lds = kP32Table + 64 * 40;
-constexpr uint32_t kP32Stage = 2592;     // bytes per half of the group's boards (32 x 81)
 constexpr uint32_t kP32Heads = 8;        // dequeue counters, one per XCD segment of the groups
 constexpr uint32_t kP32HeadStride = 32;  // words between counters (own cache lines)
 
@@ -561,37 +561,76 @@ __device__ __forceinline__ uint32_t p32_locked(const P32Lane& w, P32Cells& x) {
     return chg;
 }
 
-// One cell of the half's 32 boards, from the staging (byte of board b at col[81 b]) to its nine
-// candidate words.  Per 8 boards: the 8 bytes as a 64-bit word (byte r = board r), an 8 x 8 bit
-// transpose (three swap stages; Hacker's Delight 7-3) makes byte i the bit-i plane of the 8 boards,
-// v_perm gathers the planes of the 32 boards, and each digit's word is its minterm over the low
-// four planes (values > 9 are the inert boards, decided elsewhere), or'd with the empty cells.
-__device__ __forceinline__ void p32_convert(const p32_lds_t* col, uint32_t (&c)[9]) {
-    uint32_t lo[4];
+// A group's boards from global memory to the lane's registers, no staging: word b is the dword that
+// holds the lane's three cells of board b of its half -- bytes 3 hl .. 3 hl + 3 of the board's row, an
+// unaligned load (an ordinary instruction on global memory; in LDS it would be replayed).  Lane 26's
+// cells are the row's last three bytes, so it loads from byte 77 and its cells are bytes 1..3 of the
+// word (sh = 1; p32_planes shifts its selectors): no lane reads past its board's row, so nothing past
+// the batch's last board.  Spare lanes load lane 0's word (masked out like all their results).  A
+// ragged group (nb < 64) loads board nb - 1 in the slots past it (masked out by `valid`).
+__device__ __forceinline__ void p32_load(const uint8_t* src, uint32_t nb, uint32_t (&d)[32]) {
+    const uint32_t t = p32_opq(threadIdx.x), hl = t & 31u, b0 = t & 32u;
+    const uint32_t off = hl < 26u ? 3u * hl : (hl == 26u ? 77u : 0u);
+    if (nb == 64u) {
+        const uint8_t* p = src + (81u * b0 + off);
 #pragma unroll
-    for (int m = 0; m < 4; ++m) {
-        uint32_t l = col[81u * (8 * m)], h = col[81u * (8 * m + 4)];
+        for (int b = 0; b < 32; ++b) __builtin_memcpy(&d[b], p + 81 * b, 4);
+    } else {
 #pragma unroll
-        for (int r = 1; r < 4; ++r) {
-            l |= (uint32_t)col[81u * (8 * m + r)] << (8 * r);
-            h |= (uint32_t)col[81u * (8 * m + 4 + r)] << (8 * r);
-        }
-        uint32_t t;
-        t = (l ^ (l >> 7)) & 0x00AA00AAu;  l ^= t ^ (t << 7);
-        t = (h ^ (h >> 7)) & 0x00AA00AAu;  h ^= t ^ (t << 7);
-        t = (l ^ (l >> 14)) & 0x0000CCCCu; l ^= t ^ (t << 14);
-        t = (h ^ (h >> 14)) & 0x0000CCCCu; h ^= t ^ (t << 14);
-        t = (l ^ (h << 4)) & 0xF0F0F0F0u;  l ^= t;       // the high word is not needed after this
-        lo[m] = l;                         // byte i: plane i of boards 8m .. 8m + 7
+        for (int b = 0; b < 32; ++b) __builtin_memcpy(&d[b], src + (81u * min(b0 + b, nb - 1u) + off), 4);
     }
+}
+
+// Eight boards' words (d: boards 8m .. 8m + 7 of p32_load) to the bit planes of the lane's three
+// cells: lo[k] byte i = plane i of cell k over the eight boards; hn byte i = plane 4 + i of any of the
+// three cells (a value above 15).  Per four boards a 4 x 3 byte transpose by v_perm_b32 (seven for the
+// three cells' words -- byte r of word k = cell k of board r; sh moves the first stage's selectors by
+// a byte for lane 26), then per cell the 8 x 8 bit transpose (three swap stages; Hacker's Delight 7-3)
+// of the two words.
+__device__ __forceinline__ void p32_planes(const uint32_t* d, uint32_t sh, uint32_t (&lo)[3], uint32_t& hn) {
+    const uint32_t selA = 0x05010400u + 0x01010101u * sh, selB = 0x0C0C0602u + 0x0101u * sh;
+    uint32_t l[3], h[3];
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+        const uint32_t A = __builtin_amdgcn_perm(d[4 * q + 1], d[4 * q], selA);       // cells 0, 1 of boards 0, 1
+        const uint32_t B = __builtin_amdgcn_perm(d[4 * q + 1], d[4 * q], selB);       // cell 2
+        const uint32_t C = __builtin_amdgcn_perm(d[4 * q + 3], d[4 * q + 2], selA);   // boards 2, 3
+        const uint32_t D = __builtin_amdgcn_perm(d[4 * q + 3], d[4 * q + 2], selB);
+        uint32_t* o = q == 0 ? l : h;
+        o[0] = __builtin_amdgcn_perm(C, A, 0x05040100u);
+        o[1] = __builtin_amdgcn_perm(C, A, 0x07060302u);
+        o[2] = __builtin_amdgcn_perm(D, B, 0x05040100u);
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        uint32_t t;
+        t = (l[k] ^ (l[k] >> 7)) & 0x00AA00AAu;  l[k] ^= t ^ (t << 7);
+        t = (h[k] ^ (h[k] >> 7)) & 0x00AA00AAu;  h[k] ^= t ^ (t << 7);
+        t = (l[k] ^ (l[k] >> 14)) & 0x0000CCCCu; l[k] ^= t ^ (t << 14);
+        t = (h[k] ^ (h[k] >> 14)) & 0x0000CCCCu; h[k] ^= t ^ (t << 14);
+    }
+    // the planes 4..7 (the high nibbles: of l for boards 0..3, of h for boards 4..7), any cell
+    const uint32_t la = p32_b3<kB3Or3>(l[0], l[1], l[2]), ha = p32_b3<kB3Or3>(h[0], h[1], h[2]);
+    hn = (ha & 0xF0F0F0F0u) | ((la >> 4) & 0x0F0F0F0Fu);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) lo[k] = l[k] ^ ((l[k] ^ (h[k] << 4)) & 0xF0F0F0F0u);   // planes 0..3
+}
+
+// byte m of the result = byte i of w[m] (a 4 x 4 byte transpose's row i is p32_gather(w, i))
+__device__ __forceinline__ uint32_t p32_gather(const uint32_t (&w)[4], int i) {
+    // bytes (w[0].i, w[1].i) and (w[2].i, w[3].i); selector 0x0C = a zero byte
+    const uint32_t a = __builtin_amdgcn_perm(w[1], w[0], 0x0C0C0400u + 0x0101u * (uint32_t)i);
+    const uint32_t b = __builtin_amdgcn_perm(w[3], w[2], 0x04000C0Cu + 0x01010000u * (uint32_t)i);
+    return a | b;
+}
+
+// One cell's planes (lo[m] byte i: plane i of boards 8m .. 8m + 7) to its nine candidate words: each
+// digit's word is its minterm over the four planes, or'd with the empty cells.  Returns the boards
+// whose value is 10..15 (inert, as every value above 9: decided elsewhere).
+__device__ __forceinline__ uint32_t p32_minterms(const uint32_t (&lo)[4], uint32_t (&c)[9]) {
     uint32_t P[4];
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        // bytes (lo[0].i, lo[1].i) and (lo[2].i, lo[3].i); selector 0x0C = a zero byte
-        const uint32_t a = __builtin_amdgcn_perm(lo[1], lo[0], 0x0C0C0400u + 0x0101u * (uint32_t)i);
-        const uint32_t b = __builtin_amdgcn_perm(lo[3], lo[2], 0x04000C0Cu + 0x01010000u * (uint32_t)i);
-        P[i] = a | b;
-    }
+    for (int i = 0; i < 4; ++i) P[i] = p32_gather(lo, i);
     const uint32_t e = ~(P[0] | P[1] | P[2] | P[3]);        // empty cells: every digit
     const uint32_t n3 = ~P[3];
     c[0] = (P[0] & ~P[1] & ~P[2] & n3) | e;                 // 1 = 0001
@@ -603,30 +642,94 @@ __device__ __forceinline__ void p32_convert(const p32_lds_t* col, uint32_t (&c)[
     c[6] = (P[0] & P[1] & P[2] & n3) | e;                   // 7 = 0111
     c[7] = (P[3] & ~P[0]) | e;                              // 8 = 1000 (9 < v < 16: inert)
     c[8] = (P[3] & P[0]) | e;                               // 9 = 1001
+    return P[3] & (P[1] | P[2]);
 }
 
-// The inverse of p32_convert for one cell: the digit of each of the 32 boards (the binary planes of
-// its one-hot words, gathered 8 boards at a time and bit-transposed back into bytes) into the
-// staging, byte of board b at col[81 b]; 0 where the cell is open.  (Boards with a contradiction or
-// an inert given get meaningless bytes.)
-__device__ __forceinline__ void p32_digits(const uint32_t (&c)[9], uint32_t single, p32_lds_t* col) {
-    // open cells (more than one candidate left) come out as 0
-    const uint32_t Q[4] = {(c[0] | c[2] | c[4] | c[6] | c[8]) & single, (c[1] | c[2] | c[5] | c[6]) & single,
-                           (c[3] | c[4] | c[5] | c[6]) & single, (c[7] | c[8]) & single};
+// The lane's 32 loaded words to its three cells' candidate words; returns the boards with a value
+// above 9 in one of the three cells (only the lane's own three bytes of each word enter).
+__device__ __forceinline__ uint32_t p32_convert(const uint32_t (&d)[32], P32Cells& x) {
+    const uint32_t sh = (p32_opq(threadIdx.x) & 31u) == 26u ? 1u : 0u;
+    uint32_t lo[3][4], hn[4];
 #pragma unroll
     for (int m = 0; m < 4; ++m) {
-        // byte i: plane i of boards 8m .. 8m + 7 (the high word, planes 4..7, is zero)
-        const uint32_t a = __builtin_amdgcn_perm(Q[1], Q[0], 0x0C0C0400u + 0x0101u * (uint32_t)m);
-        const uint32_t b = __builtin_amdgcn_perm(Q[3], Q[2], 0x04000C0Cu + 0x01010000u * (uint32_t)m);
-        uint32_t l = a | b, t;
-        t = (l ^ (l >> 7)) & 0x00AA00AAu;  l ^= t ^ (t << 7);
-        t = (l ^ (l >> 14)) & 0x0000CCCCu; l ^= t ^ (t << 14);
-        const uint32_t h = (l >> 4) & 0x0F0F0F0Fu;   // boards 8m + 4 .. 8m + 7
-        l &= 0x0F0F0F0Fu;                             // boards 8m .. 8m + 3
+        uint32_t l3[3];
+        p32_planes(d + 8 * m, sh, l3, hn[m]);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) lo[k][m] = l3[k];
+    }
+    uint32_t hi = p32_gather(hn, 0) | p32_gather(hn, 1) | p32_gather(hn, 2) | p32_gather(hn, 3);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) hi |= p32_minterms(lo[k], x.c[k]);
+    return hi;
+}
+
+// The answers' staging: the group's 64 x 27 cell triads as one dword each, (d0, d1, d2, 0) -- triad
+// j of board p (of the group) at 108 p + 4 j, so byte G of the group's 5,184 output bytes is at
+// G + G / 3, cell c of board p at p32_stage_byte(p, c).  32 boards x 108 B = kP32Region: the two
+// halves' stagings lie back to back over the two regions.  A lane stores its triad of a board with one
+// aligned ds_write_b32 (27 consecutive dwords per half: no two lanes of a half in one bank), and the
+// store phase reads four triads with one ds_read_b128 (p32_store_group).
+__device__ __forceinline__ uint32_t p32_stage_byte(uint32_t p, uint32_t c) { return 108u * p + c + c / 3u; }
+
+// The inverse of the conversion for the lane's three cells: the digit of each of the 32 boards (the
+// binary planes of the one-hot words, gathered 8 boards at a time and bit-transposed back into bytes),
+// 0 where the cell is open, combined by v_perm_b32 into the board's triad word and stored at
+// tri[27 b] (tri: the lane's triad of the half's board 0).  (Boards with a contradiction or an inert
+// given get meaningless bytes.)
+__device__ __forceinline__ void p32_digits(const P32Cells& x, p32_lds_t* tri) {
+    uint32_t Q[3][4];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        // open cells (more than one candidate left) come out as 0
+        const uint32_t* c = x.c[k];
+        const uint32_t single = x.s[k];
+        Q[k][0] = (c[0] | c[2] | c[4] | c[6] | c[8]) & single;
+        Q[k][1] = (c[1] | c[2] | c[5] | c[6]) & single;
+        Q[k][2] = (c[3] | c[4] | c[5] | c[6]) & single;
+        Q[k][3] = (c[7] | c[8]) & single;
+    }
+    __attribute__((address_space(3))) uint32_t* out = (__attribute__((address_space(3))) uint32_t*)tri;
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+        uint32_t l[3], h[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            // byte i: plane i of boards 8m .. 8m + 7 (the high word, planes 4..7, is zero)
+            uint32_t v = p32_gather(Q[k], m), t;
+            t = (v ^ (v >> 7)) & 0x00AA00AAu;  v ^= t ^ (t << 7);
+            t = (v ^ (v >> 14)) & 0x0000CCCCu; v ^= t ^ (t << 14);
+            h[k] = (v >> 4) & 0x0F0F0F0Fu;   // boards 8m + 4 .. 8m + 7
+            l[k] = v & 0x0F0F0F0Fu;          // boards 8m .. 8m + 3
+        }
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            col[81u * (8 * m + r)] = (uint8_t)(l >> (8 * r));
-            col[81u * (8 * m + 4 + r)] = (uint8_t)(h >> (8 * r));
+            // (cell 0, cell 1, 0, 0) of board r, then cell 2 into byte 2
+            const uint32_t s01 = 0x0C0C0400u + 0x0101u * (uint32_t)r, s2 = 0x0C040100u + 0x00010000u * (uint32_t)r;
+            out[27 * (8 * m + r)] = __builtin_amdgcn_perm(l[2], __builtin_amdgcn_perm(l[1], l[0], s01), s2);
+            out[27 * (8 * m + 4 + r)] = __builtin_amdgcn_perm(h[2], __builtin_amdgcn_perm(h[1], h[0], s01), s2);
+        }
+    }
+}
+
+// A full group's 5,184 answer bytes from the staging to dst: lane t takes the triads 4u .. 4u + 3,
+// u = t + 64 i, with one ds_read_b128 (16-byte aligned, a lane's 16 bytes contiguous: the access the
+// LDS serves at full width), packs their 12 bytes with three v_perm_b32 and stores them at dst + 12u.
+// A wave's store covers 768 contiguous bytes from a 64-byte boundary.
+struct __attribute__((packed, aligned(4))) p32_u3 {
+    uint32_t a, b, c;
+};
+__device__ __forceinline__ void p32_store_group(const p32_lds_t* lds, uint8_t* dst) {
+    const uint32_t t = p32_opq(threadIdx.x);
+#pragma unroll
+    for (int i = 0; i < 7; ++i) {
+        const uint32_t u = t + 64u * i;
+        if (i < 6 || t < 48u) {      // 432 = 6 x 64 + 48 pieces
+            const p32_u4 v = *(const __attribute__((address_space(3))) p32_u4*)(lds + 16u * u);
+            p32_u3 o;
+            o.a = __builtin_amdgcn_perm(v[1], v[0], 0x04020100u);
+            o.b = __builtin_amdgcn_perm(v[2], v[1], 0x05040201u);
+            o.c = __builtin_amdgcn_perm(v[3], v[2], 0x06050402u);
+            *reinterpret_cast<p32_u3*>(dst + 12u * u) = o;
         }
     }
 }
@@ -763,52 +866,18 @@ __device__ __forceinline__ void prop32_body(Prop32Args a, uint64_t* stamps) {
         if (g == ~0u) break;
         const uint64_t base = (uint64_t)g * 64;
         const uint32_t nb = (uint32_t)min<uint64_t>(64, a.n - base);
-        // the group's boards into the staging (row-major, 81 bytes each; half h: boards 32h..)
         const uint8_t* src = a.in + base * 81;
-        bool hi_given = true;      // a byte > 9 may be in the group: find the inert boards one by one
-        if (nb == 64) {
-            // 324 pieces of 16 B: 5 per lane, 4 lanes a sixth; piece q of the group to the staging of
-            // half q / 162.  Every byte is also tested for > 9 (bytewise, exact: the high bit of
-            // (b & 0x7F) + 0x76, or of b itself)
-            const uint32_t t = p32_opq(threadIdx.x);
-            p32_u4 v[6];
-#pragma unroll
-            for (int i = 0; i < 6; ++i)
-                if (i < 5 || t < 4u) v[i] = reinterpret_cast<const p32_u4*>(src)[t + 64u * i];
-            uint32_t hi = 0u;
-#pragma unroll
-            for (int i = 0; i < 6; ++i) {
-                const uint32_t q = t + 64u * i, h = q >= 162u ? 1u : 0u;
-                if (i < 5 || t < 4u) {
-                    *(__attribute__((address_space(3))) p32_u4*)(lds + h * (kP32Region - kP32Stage) + 16u * q) = v[i];
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) hi |= ((v[i][e] & 0x7F7F7F7Fu) + 0x76767676u) | v[i][e];
-                }
-            }
-            hi_given = __builtin_amdgcn_ballot_w64((hi & 0x80808080u) != 0u) != 0ull;
-        } else {
-            for (uint32_t o = threadIdx.x; o < nb * 81u; o += 64u) {
-                const uint32_t h = o >= kP32Stage ? 1u : 0u;
-                lds[h * kP32Region + o - h * kP32Stage] = src[o];
-            }
-        }
-        __builtin_amdgcn_wave_barrier();
-        // the boards with a given > 9 (inert cells, undecided here): lane L scans board L's row
-        uint64_t inert64 = 0ull;
-        if (hi_given) {
-            bool bad = false;
-            const uint32_t t = p32_opq(threadIdx.x);   // (per-lane values recomputed per group: hoisted
-            if (t < nb) {                               // out of the group loop they were spilled)
-                const p32_lds_t* row = lds + (t >> 5) * kP32Region + (t & 31u) * 81u;
-                for (uint32_t c = 0; c < 81u; ++c) bad |= row[c] > 9u;
-            }
-            inert64 = __builtin_amdgcn_ballot_w64(bad);
-        }
-        // bit-sliced candidate words: digit v -> one word, 0 -> all nine (boards with a given > 9 are
-        // undecided; their words do not matter)
+        // the group's boards into registers and on to the bit-sliced candidate words: digit v -> one
+        // word, 0 -> all nine; the boards with a given > 9 (inert cells, undecided here; their words do
+        // not matter) from the same planes
         P32Cells x;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) p32_convert(w.reg + 3u * w.hl + k, x.c[k]);
+        uint64_t inert64;
+        {
+            uint32_t d[32];
+            p32_load(src, nb, d);
+            const uint32_t hi = p32_convert(d, x);
+            inert64 = p32_mask64(p32_half_or(w.act ? hi : 0u));
+        }
         // per-group bookkeeping as 64-bit board masks in scalar registers (bit 32h + b: board b of
         // half h)
         const uint64_t valid = nb >= 64u ? ~0ull : ((1ull << nb) - 1ull);
@@ -918,35 +987,21 @@ __device__ __forceinline__ void prop32_body(Prop32Args a, uint64_t* stamps) {
             handed &= ~dupw;
             __builtin_amdgcn_wave_barrier();
         }
-        if ((solved | handed) && w.act) {
-#pragma unroll
-            for (int k = 0; k < 3; ++k) p32_digits(x.c[k], x.s[k], w.reg + 3u * w.hl + k);
-        }
+        if ((solved | handed) && w.act) p32_digits(x, w.reg + 4u * w.hl);
         for (uint64_t m = contra; m; m &= m - 1ull) {     // rare: the 81 bytes by 64 lanes
             const uint32_t p = (uint32_t)__builtin_ctzll(m);
             const uint8_t* s = a.in + (base + p) * 81;
-            p32_lds_t* d = lds + (p >> 5) * kP32Region + (p & 31u) * 81u;
-            d[threadIdx.x] = s[threadIdx.x];
-            if (threadIdx.x < 17u) d[64 + threadIdx.x] = s[64 + threadIdx.x];
+            lds[p32_stage_byte(p, threadIdx.x)] = s[threadIdx.x];
+            if (threadIdx.x < 17u) lds[p32_stage_byte(p, 64u + threadIdx.x)] = s[64 + threadIdx.x];
         }
         __builtin_amdgcn_wave_barrier();
         if (solved | contra) {
             // undecided boards' rows get what the staging holds; the search's answers replace them
             uint8_t* dst = a.out + base * 81;
             if (nb == 64) {
-                const uint32_t t = p32_opq(threadIdx.x);
-#pragma unroll
-                for (int i = 0; i < 6; ++i) {
-                    const uint32_t q = t + 64u * i, h = q >= 162u ? 1u : 0u;
-                    if (i < 5 || t < 4u)
-                        reinterpret_cast<p32_u4*>(dst)[q] =
-                            *(const __attribute__((address_space(3))) p32_u4*)(lds + h * (kP32Region - kP32Stage) + 16u * q);
-                }
+                p32_store_group(lds, dst);
             } else {
-                for (uint32_t o = threadIdx.x; o < nb * 81u; o += 64u) {
-                    const uint32_t h = o >= kP32Stage ? 1u : 0u;
-                    dst[o] = lds[h * kP32Region + o - h * kP32Stage];
-                }
+                for (uint32_t o = threadIdx.x; o < nb * 81u; o += 64u) dst[o] = lds[o + o / 3u];
             }
         }
         // statuses; the undecided boards are listed with their inputs for the search
@@ -964,9 +1019,8 @@ __device__ __forceinline__ void prop32_body(Prop32Args a, uint64_t* stamps) {
                 const uint32_t p = (uint32_t)__builtin_ctzll(m);
                 uint8_t* d = a.list_in + (uint64_t)k * 81;
                 if ((handed >> p) & 1ull) {      // the propagated grid, from the staging
-                    const p32_lds_t* s = lds + (p >> 5) * kP32Region + (p & 31u) * 81u;
-                    d[threadIdx.x] = s[threadIdx.x];
-                    if (threadIdx.x < 17u) d[64 + threadIdx.x] = s[64 + threadIdx.x];
+                    d[threadIdx.x] = lds[p32_stage_byte(p, threadIdx.x)];
+                    if (threadIdx.x < 17u) d[64 + threadIdx.x] = lds[p32_stage_byte(p, 64u + threadIdx.x)];
                 } else {
                     const uint8_t* s = a.in + (base + p) * 81;
                     d[threadIdx.x] = s[threadIdx.x];
