@@ -21,6 +21,7 @@ SDK_ECOMM = -4
 SDK_SOLVED = 1
 SDK_UNSOLVABLE = 0
 SDK_BUDGET_HIT = -2
+SDK_MULTIPLE = 2      # sdk_classify_batch / sdk_minimize_batch only: at least two completions
 SDK_BUDGET_CONTEXT = (1 << 64) - 1    # sdk_solve_batch_budget: use the context's SDK_OPT_NODE_BUDGET
 
 SDK_CHECK_OK = 1
@@ -106,6 +107,10 @@ SIGNATURES = {
     "sdk_solve_batch": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _sz]),
     "sdk_solve_batch_budget": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, ctypes.c_uint64]),
     "sdk_solve_batch_ex": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, ctypes.c_uint64, ctypes.c_int64]),
+    "sdk_classify_batch": (ctypes.c_int, [_vp, _vp, _vp, _vp, _sz, ctypes.c_uint64]),
+    "sdk_classify_batch_dev": (ctypes.c_int, [_vp, _vp, _vp, _vp, _sz, ctypes.c_uint64]),
+    "sdk_minimize_batch": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _sz]),
+    "sdk_minimize_batch_dev": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _sz]),
     "sdk_frontier_boards_dev": (ctypes.c_int, [_vp, ctypes.POINTER(_vp), ctypes.POINTER(ctypes.c_uint64)]),
     "sdk_frontier_load_dev": (ctypes.c_int, [_vp, _vp, ctypes.c_uint64]),
     "sdk_frontier_refine_range": (ctypes.c_int, [_vp, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64,

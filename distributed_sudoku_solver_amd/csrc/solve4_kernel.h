@@ -1606,7 +1606,8 @@ __device__ __forceinline__ void split_save4(const Lane4& w, const Args4& a, cons
 // DFS level record: every lane keeps the level's branch record -- cell | untried
 // digits << 7, uniform in the half -- in the free upper 16 bits of its own snapshot
 // word y, so a level is one 8-byte word per lane and needs no shared record array.
-template <bool DN, int HI, bool SV = false, bool FS = false>
+// CL: a classify launch (ORDER_CLASSIFY): a board's second completion ends it as kStMultiple
+template <bool DN, int HI, bool SV = false, bool FS = false, bool CL = false>
 __device__ __forceinline__ void step4_body(const Lane4& w, const Lane4& wr, const Args4& a, Slot4& b, Cells4& c, bool bad,
                                            uint2 (*s_stk)[2][64], uint2* g_stk) {
     ++b.nodes;
@@ -1683,7 +1684,9 @@ __device__ __forceinline__ void step4_body(const Lane4& w, const Lane4& wr, cons
             if (w.hl == 0) atomicAdd(&s_count4, (unsigned long long)(b.count - 1u));
             b.count = 1;
         } else if (b.count >= b.lim) {
-            if (b.order == ORDER_MRV && !a.count_mode) {      // >= 2 completions: lex re-search
+            if (CL) {                                          // classify: the second completion is the verdict
+                PROF4(3, finish_board4<DN, HI, FS>(w, wr, a, b, c, kStMultiple));
+            } else if (b.order == ORDER_MRV && !a.count_mode) {      // >= 2 completions: lex re-search
                 b.order = ORDER_LEX;
                 b.lim = 1;
                 start_board4<HI>(w, a, b, c, false);
@@ -1768,14 +1771,14 @@ backtrack:
 }
 
 // step of slot HI: its state comes from and returns to LDS; returns whether the slot is active
-template <bool DN, int HI, bool SV = false, bool FS = false>
+template <bool DN, int HI, bool SV = false, bool FS = false, bool CL = false>
 __device__ __forceinline__ bool step4(const Lane4& wr, const Args4& a, Cells4& c, bool bad, uint2 (*s_stk)[2][64],
                                       uint2* g_stk_all, Slot4* s_slot, uint2* s_region, uint8_t* s_in) {
     const Lane4 w = lane4_fresh(s_region, s_in);
     uint2* g_stk = g_stk_all + (size_t)blockIdx.x * (kMaxDepth * 2 * 64);
     Slot4* p = s_slot + w.half * 2 + HI;
     Slot4 b;
-    PROF4(1 + HI, b = *p; step4_body<DN, HI, SV, FS>(w, wr, a, b, c, bad, s_stk, g_stk); if (w.hl == 0) *p = b);
+    PROF4(1 + HI, b = *p; step4_body<DN, HI, SV, FS, CL>(w, wr, a, b, c, bad, s_stk, g_stk); if (w.hl == 0) *p = b);
     return (b.active & 1u) != 0u;
 }
 
@@ -1801,8 +1804,9 @@ __device__ __forceinline__ bool first_board4(const Lane4& w, const Args4& a, Cel
 #define SDK_SOLVE4_DN_WAVES_PER_EU 5
 #endif
 // SV: the split phase of a phased solve (split_save4); FS: a first-solution scan of a lex frontier
-// (boards above the lowest hit are cancelled, see s_found4)
-template <bool DN, bool SV = false, bool FS = false>
+// (boards above the lowest hit are cancelled, see s_found4); CL: a classify launch (SolveArgs::order
+// is ORDER_CLASSIFY; an instantiation of its own, so the others keep their registers)
+template <bool DN, bool SV = false, bool FS = false, bool CL = false>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(DN ? SDK_SOLVE4_DN_WAVES_PER_EU : SDK_SOLVE4_WAVES_PER_EU))) void solve4_kernel(SolveArgs args) {
     // the donation phases are enqueued without the host: their board count comes from the
     // device (the list the previous phase left), and the launch is the full resident grid, of
@@ -1931,13 +1935,13 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(DN ? SDK_SOL
         if (E0 != 0) {
             bool r = false;
             if (__builtin_amdgcn_inverse_ballot_w64(E0))
-                r = step4<DN, 0, SV, FS>(w, a, c, __builtin_amdgcn_inverse_ballot_w64(B0), s_stk, g_stk, s_slot, s_region, s_in);
+                r = step4<DN, 0, SV, FS, CL>(w, a, c, __builtin_amdgcn_inverse_ballot_w64(B0), s_stk, g_stk, s_slot, s_region, s_in);
             A0 = (A0 & ~E0) | (__builtin_amdgcn_ballot_w64(r) & E0);
         }
         if (E1 != 0) {
             bool r = false;
             if (__builtin_amdgcn_inverse_ballot_w64(E1))
-                r = step4<DN, 1, SV, FS>(w, a, c, __builtin_amdgcn_inverse_ballot_w64(B1), s_stk, g_stk, s_slot, s_region, s_in);
+                r = step4<DN, 1, SV, FS, CL>(w, a, c, __builtin_amdgcn_inverse_ballot_w64(B1), s_stk, g_stk, s_slot, s_region, s_in);
             A1 = (A1 & ~E1) | (__builtin_amdgcn_ballot_w64(r) & E1);
         }
         if (DN && (E0 | E1) != 0) {

@@ -77,7 +77,10 @@ constexpr uint32_t kChunk = 4;        // expand_kernel chunk; solve_kernel takes
 constexpr int kStackWordsPerBlock = kMaxDepth * 64;
 
 enum { P_CONTRA = 0, P_SOLVED = 1, P_OPEN = 2 };
-enum { ORDER_MRV = 0, ORDER_LEX = 1 };
+// ORDER_CLASSIFY (sdk_classify_batch, QUAD solver only; not an SDK_ORDER_*): MRV search for at most
+// two completions like ORDER_MRV, but the second one ends the board as kStMultiple with its input
+// restored instead of starting the LEX re-search
+enum { ORDER_MRV = 0, ORDER_LEX = 1, ORDER_CLASSIFY = 2 };
 
 struct SolveArgs {
     const uint8_t* in;
@@ -89,7 +92,7 @@ struct SolveArgs {
     uint32_t* next;            // work counter (zeroed before launch)
     uint32_t* stack;           // gridDim.x * kStackWordsPerBlock words
     uint64_t budget;           // nodes per board, 0 = unlimited
-    int order;                 // SDK_ORDER_*
+    int order;                 // SDK_ORDER_*, or ORDER_CLASSIFY
     uint64_t limit;            // count mode: per-board completion limit (0 = none)
     unsigned long long* count; // count mode: running total over the batch (atomic)
     unsigned long long* counts;// count mode: per-board counts (nullable)
@@ -116,6 +119,8 @@ struct SolveArgs {
 constexpr uint64_t kBudgetBigBoards = 1ull << 19;
 // status of a board a first-solution scan stopped because it lies above a lower board's hit
 constexpr int kStCancelled = -3;
+// status of a classified board with at least two completions (SDK_MULTIPLE)
+constexpr int kStMultiple = 2;
 
 // per-XCD dequeue: the first n - n/128 boards are cut into kHeads contiguous segments with a
 // head each, workgroup g takes chunks of segment g % kHeads (the XCD the round-robin

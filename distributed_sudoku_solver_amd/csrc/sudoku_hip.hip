@@ -23,6 +23,7 @@
 #include "solve2_kernel.h"   // constants only: the kernel lives in solve2_launch.hip
 #include "solve4_kernel.h"   // constants only: the kernel lives in solve4_launch.hip
 #include "prop32_kernel.h"   // constants only: the kernel lives in prop32_launch.hip
+#include "minimize_kernel.h"
 #define SDK_DEFINE_LANE_KERNEL
 #include "solve_lane_kernel.h"
 
@@ -371,6 +372,8 @@ struct sdk_ctx {
     int clock_probe = 0;           // sdk_debug_clock_arm: prop32 passes run the stamped twin
     DevBuf p32_stamps;             // ... its stamps, 4 words per workgroup of the last such pass
     uint32_t p32_stamp_wgs = 0;
+    DevBuf mz_cand, mz_out, mz_st; // sdk_minimize_batch: a round's candidates, their classify outputs and verdicts
+    DevBuf mz_order;               // ... the host-pointer call's order rows
     DevBuf fr_a, fr_b, prop, bcell, bmask, nchild, offs, fr_status, fr_mask, tsum, fr_ctl;
     DevBuf fr_tail;                // refine_head: the boards kept after the refined ones
     // the device-resident frontier of the last sdk_frontier_build (in fr_a)
@@ -893,6 +896,7 @@ int launch_prop32_solve(sdk_ctx* c, const uint8_t* d_in, uint8_t* d_out, int8_t*
     }
     HIPCALL(sdk::launch_prop32(a, grid, c->stream, stamps));
     if ((rc = timer_end(c, stop)) || (rc = timer_begin(c, &stop))) return rc;
+    const bool held = c->timer_hold;   // a minimise call holds the timer over all its rounds
     c->timer_hold = true;
     c->prop32_ran = true;
     const uint32_t* lst = static_cast<const uint32_t*>(c->p32_list.p);
@@ -906,7 +910,73 @@ int launch_prop32_solve(sdk_ctx* c, const uint8_t* d_in, uint8_t* d_out, int8_t*
                                     d_out, d_status, g, c->stream) != hipSuccess)
             rc = fail(SDK_EHIP, "prop32 scatter launch failed");
     }
-    c->timer_hold = false;
+    c->timer_hold = held;
+    if (rc) return rc;
+    return timer_end(c, stop);
+}
+
+// Classify launch (sdk_classify_batch): the solve path with ORDER_CLASSIFY -- the prop32 pass under
+// the conditions a plain solve gets it (its statuses 1 and 0 are already "exactly one" and "none"),
+// then ONE plain QUAD launch over the boards it left (no phases, no donation: launch_solve's
+// two_phase is false for this order), whatever SDK_OPT_SOLVER and SDK_OPT_ORDER say.  Batches above
+// kDnCapBoards (the pass's cap) go in slices of that many, so every slice gets the pass.
+// Nothing of the call outlives it: the solver option is put back, and dn_ran, dn_resume_now and
+// split_big are left as a one-launch solve leaves them.
+int launch_classify(sdk_ctx* c, const uint8_t* d_in, uint8_t* d_out, int8_t* d_status, size_t n, int64_t budget) {
+    const int solver = c->solver;
+    c->solver = SDK_SOLVER_QUAD;
+    int rc = SDK_OK;
+    for (uint64_t b0 = 0; b0 < n && !rc; b0 += kDnCapBoards) {
+        const uint64_t m = std::min<uint64_t>(n - b0, kDnCapBoards);
+        rc = launch_solve(c, d_in + b0 * 81, nullptr, d_out + b0 * 81, d_status + b0, nullptr, m, 0, 0, nullptr,
+                          nullptr, 0, 1, sdk::ORDER_CLASSIFY, budget, 0);
+    }
+    c->solver = solver;
+    c->split_big = 0;
+    return rc;
+}
+
+// Greedy clue removal (sdk_minimize_batch; minimize_kernel.h): the inputs' verdicts, then 81 rounds
+// of (round kernel, classify of the candidates with no budget) and a last commit, all enqueued on
+// the stream with no host synchronisation.  Under SDK_OPT_TIMING the whole call is one span.
+// Batches above kDnCapBoards go in slices of that many (a slice's 81 rounds, then the next).
+int launch_minimize(sdk_ctx* c, const uint8_t* d_in, const uint8_t* d_order, uint8_t* d_out, int8_t* d_status,
+                    size_t n) {
+    if (n == 0) return SDK_OK;
+    if ((reinterpret_cast<uintptr_t>(d_in) | reinterpret_cast<uintptr_t>(d_out)) & 15u)
+        return fail(SDK_EINVAL, "device boards must be 16-byte aligned");
+    const uint64_t cap = std::min<uint64_t>(n, kDnCapBoards);
+    int rc;
+    if ((rc = ensure(c->mz_cand, cap * 81)) || (rc = ensure(c->mz_out, cap * 81)) || (rc = ensure(c->mz_st, cap)))
+        return rc;
+    hipEvent_t stop;
+    if ((rc = timer_begin(c, &stop))) return rc;
+    const bool held = c->timer_hold;
+    c->timer_hold = true;
+    uint8_t* cand = static_cast<uint8_t*>(c->mz_cand.p);
+    uint8_t* scratch = static_cast<uint8_t*>(c->mz_out.p);
+    int8_t* cst = static_cast<int8_t*>(c->mz_st.p);
+    for (uint64_t b0 = 0; b0 < n && !rc; b0 += kDnCapBoards) {
+        const uint64_t m = std::min<uint64_t>(n - b0, kDnCapBoards);
+        sdk::MinRoundArgs a{};
+        a.cur = d_out + b0 * 81;
+        a.order = d_order + b0 * 81;
+        a.status = d_status + b0;
+        a.cst = cst;
+        a.n = m;
+        const unsigned grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((m * 81 + 1023) / 1024, (uint64_t)c->cus * 8));
+        // the inputs' verdicts (the completions go to scratch: `out` starts as the inputs)
+        rc = launch_classify(c, d_in + b0 * 81, scratch, d_status + b0, m, 0);
+        for (uint32_t q = 0; q <= 81 && !rc; ++q) {
+            a.src = q == 0 ? d_in + b0 * 81 : a.cur;
+            a.cand = q < 81 ? cand : nullptr;
+            a.q = q;
+            sdk::minimize_round_kernel<<<grid, 256, 0, c->stream>>>(a);
+            if (hipGetLastError() != hipSuccess) rc = fail(SDK_EHIP, "minimise round launch failed");
+            if (!rc && q < 81) rc = launch_classify(c, cand, scratch, cst, m, 0);
+        }
+    }
+    c->timer_hold = held;
     if (rc) return rc;
     return timer_end(c, stop);
 }
@@ -1759,6 +1829,107 @@ int sdk_solve_batch_ex(sdk_ctx* c, const uint8_t* in, const uint16_t* first_cell
         if (work) std::memcpy(work, s_work, n * 8);
     }
     return dn_check_error(c);
+}
+
+int sdk_classify_batch_dev(sdk_ctx* c, const void* d_in, void* d_out, void* d_status, size_t n, uint64_t node_budget) {
+    if (!c || (n && (!d_in || !d_out || !d_status))) return fail(SDK_EINVAL, "NULL argument");
+    if (node_budget != SDK_BUDGET_CONTEXT && node_budget > (uint64_t)INT64_MAX)
+        return fail(SDK_EINVAL, "node budget out of range");
+    if (n == 0) return SDK_OK;
+    if (n > 0x7FFFFFFFull) return fail(SDK_EINVAL, "at most 2^31-1 boards per call");
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCALL(hipSetDevice(c->device));
+    return launch_classify(c, static_cast<const uint8_t*>(d_in), static_cast<uint8_t*>(d_out),
+                           static_cast<int8_t*>(d_status), n,
+                           node_budget == SDK_BUDGET_CONTEXT ? -1 : (int64_t)node_budget);
+}
+
+int sdk_classify_batch(sdk_ctx* c, const uint8_t* in, uint8_t* out, int8_t* status, size_t n, uint64_t node_budget) {
+    if (!c || (n && (!in || !out || !status))) return fail(SDK_EINVAL, "NULL argument");
+    if (node_budget != SDK_BUDGET_CONTEXT && node_budget > (uint64_t)INT64_MAX)
+        return fail(SDK_EINVAL, "node budget out of range");
+    if (n == 0) return SDK_OK;
+    if (n > 0x7FFFFFFFull) return fail(SDK_EINVAL, "at most 2^31-1 boards per call");
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCALL(hipSetDevice(c->device));
+    int rc;
+    if ((rc = ensure(c->in, n * 81)) || (rc = ensure(c->out, n * 81)) || (rc = ensure(c->status, n))) return rc;
+    // staging layout: in / out boards (n x 81), status (n)
+    char* st = static_cast<char*>(stage_host(c->stage, n * 82));
+    uint8_t* s_io = reinterpret_cast<uint8_t*>(st);
+    int8_t* s_st = st ? reinterpret_cast<int8_t*>(st + n * 81) : nullptr;
+    if (st) std::memcpy(s_io, in, n * 81);
+    DrainOnError drain{c->stream, st != nullptr};
+    HIPCALL(hipMemcpyAsync(c->in.p, st ? s_io : in, n * 81, hipMemcpyHostToDevice, c->stream));
+    if ((rc = launch_classify(c, static_cast<uint8_t*>(c->in.p), static_cast<uint8_t*>(c->out.p),
+                              static_cast<int8_t*>(c->status.p), n,
+                              node_budget == SDK_BUDGET_CONTEXT ? -1 : (int64_t)node_budget)))
+        return rc;
+    HIPCALL(hipMemcpyAsync(st ? s_io : out, c->out.p, n * 81, hipMemcpyDeviceToHost, c->stream));
+    HIPCALL(hipMemcpyAsync(st ? s_st : status, c->status.p, n, hipMemcpyDeviceToHost, c->stream));
+    HIPCALL(hipStreamSynchronize(c->stream));
+    drain.armed = false;
+    if (st) {
+        std::memcpy(out, s_io, n * 81);
+        std::memcpy(status, s_st, n);
+    }
+    return SDK_OK;
+}
+
+int sdk_minimize_batch_dev(sdk_ctx* c, const void* d_in, const void* d_order, void* d_out, void* d_status, size_t n) {
+    if (!c || (n && (!d_in || !d_order || !d_out || !d_status))) return fail(SDK_EINVAL, "NULL argument");
+    if (n == 0) return SDK_OK;
+    if (n > 0x7FFFFFFFull) return fail(SDK_EINVAL, "at most 2^31-1 boards per call");
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCALL(hipSetDevice(c->device));
+    return launch_minimize(c, static_cast<const uint8_t*>(d_in), static_cast<const uint8_t*>(d_order),
+                           static_cast<uint8_t*>(d_out), static_cast<int8_t*>(d_status), n);
+}
+
+int sdk_minimize_batch(sdk_ctx* c, const uint8_t* in, const uint8_t* order, uint8_t* out, int8_t* status, size_t n) {
+    if (!c || (n && (!in || !order || !out || !status))) return fail(SDK_EINVAL, "NULL argument");
+    if (n == 0) return SDK_OK;
+    if (n > 0x7FFFFFFFull) return fail(SDK_EINVAL, "at most 2^31-1 boards per call");
+    // every order row is a permutation of 0..80
+    for (size_t i = 0; i < n; ++i) {
+        bool seen[81] = {};
+        for (int q = 0; q < 81; ++q) {
+            const uint8_t v = order[i * 81 + q];
+            if (v >= 81 || seen[v])
+                return fail(SDK_EINVAL, "order row %zu is not a permutation of 0..80 (entry %d = %u)", i, q, (unsigned)v);
+            seen[v] = true;
+        }
+    }
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCALL(hipSetDevice(c->device));
+    int rc;
+    if ((rc = ensure(c->in, n * 81)) || (rc = ensure(c->mz_order, n * 81)) || (rc = ensure(c->out, n * 81)) ||
+        (rc = ensure(c->status, n)))
+        return rc;
+    // staging layout: order rows (n x 81), in / out boards (n x 81), status (n)
+    char* st = static_cast<char*>(stage_host(c->stage, n * 163));
+    uint8_t* s_ord = reinterpret_cast<uint8_t*>(st);
+    uint8_t* s_io = st ? reinterpret_cast<uint8_t*>(st + n * 81) : nullptr;
+    int8_t* s_st = st ? reinterpret_cast<int8_t*>(st + n * 162) : nullptr;
+    if (st) {
+        std::memcpy(s_ord, order, n * 81);
+        std::memcpy(s_io, in, n * 81);
+    }
+    DrainOnError drain{c->stream, st != nullptr};
+    HIPCALL(hipMemcpyAsync(c->in.p, st ? s_io : in, n * 81, hipMemcpyHostToDevice, c->stream));
+    HIPCALL(hipMemcpyAsync(c->mz_order.p, st ? s_ord : order, n * 81, hipMemcpyHostToDevice, c->stream));
+    if ((rc = launch_minimize(c, static_cast<uint8_t*>(c->in.p), static_cast<uint8_t*>(c->mz_order.p),
+                              static_cast<uint8_t*>(c->out.p), static_cast<int8_t*>(c->status.p), n)))
+        return rc;
+    HIPCALL(hipMemcpyAsync(st ? s_io : out, c->out.p, n * 81, hipMemcpyDeviceToHost, c->stream));
+    HIPCALL(hipMemcpyAsync(st ? s_st : status, c->status.p, n, hipMemcpyDeviceToHost, c->stream));
+    HIPCALL(hipStreamSynchronize(c->stream));
+    drain.armed = false;
+    if (st) {
+        std::memcpy(out, s_io, n * 81);
+        std::memcpy(status, s_st, n);
+    }
+    return SDK_OK;
 }
 
 int sdk_count_solutions(sdk_ctx* c, const uint8_t* board, uint64_t limit, uint64_t* count, int8_t* status) {

@@ -286,6 +286,51 @@ class SudokuEngine:
             self.set_option(L.SDK_OPT_DONATE, old)
         return out, status, work
 
+    def classify_batch(self, boards, budget=None):
+        """uint8[n,81] -> (status int8[n], out uint8[n,81]): does each board have no completion
+        (SDK_UNSOLVABLE), exactly one (SDK_SOLVED, out = that completion) or several
+        (SDK_MULTIPLE)?  out is the input for every status but SDK_SOLVED.  budget as in
+        solve_batch (a board that runs out is SDK_BUDGET_HIT)."""
+        boards = np.ascontiguousarray(boards, dtype=np.uint8).reshape(-1, 81)
+        n = boards.shape[0]
+        if budget is not None and not 0 <= int(budget) < (1 << 63):
+            raise ValueError("budget must be 0 (unlimited) or a positive node count")
+        out = np.empty_like(boards)
+        status = np.empty(n, dtype=np.int8)
+        L.check(self.lib.sdk_classify_batch(self.ctx, _ptr(boards), _ptr(out), _ptr(status), n,
+                                            L.SDK_BUDGET_CONTEXT if budget is None else int(budget)),
+                "sdk_classify_batch")
+        return status, out
+
+    @staticmethod
+    def check_order(order, n):
+        """order -> uint8[n,81], every row a permutation of 0..80 (else ValueError)."""
+        order = np.asarray(order)
+        if order.size != n * 81:
+            raise ValueError(f"order must be [{n}, 81]")
+        wide = order.reshape(n, 81).astype(np.int64, copy=False)
+        if n and not (np.sort(wide, axis=1) == np.arange(81)).all():
+            raise ValueError("every order row must be a permutation of 0..80")
+        return np.ascontiguousarray(wide, dtype=np.uint8)
+
+    def minimize_batch(self, boards, order=None, seed=0):
+        """uint8[n,81] -> (puzzles uint8[n,81], status int8[n]): greedy clue removal on the GPU
+        (sdk_minimize_batch).  status[i] is classify_batch's verdict of board i; a board that is
+        not SDK_SOLVED comes back unchanged, the others lose, in the cell order of order[i]
+        (uint8[n,81], a permutation of 0..80 per row), every clue without which they still have
+        exactly one completion.  order=None draws one permutation per board from
+        np.random.default_rng(seed).  A bad order raises ValueError before any launch."""
+        boards = np.ascontiguousarray(boards, dtype=np.uint8).reshape(-1, 81)
+        n = boards.shape[0]
+        if order is None:
+            order = np.random.default_rng(seed).permuted(np.tile(np.arange(81, dtype=np.uint8), (n, 1)), axis=1)
+        order = self.check_order(order, n)
+        out = np.empty_like(boards)
+        status = np.empty(n, dtype=np.int8)
+        L.check(self.lib.sdk_minimize_batch(self.ctx, _ptr(boards), _ptr(order), _ptr(out), _ptr(status), n),
+                "sdk_minimize_batch")
+        return out, status
+
     def expand(self, boards, masks=None, target=64):
         """Lex-ordered frontier below `boards` (sdk_expand_boards): uint8[k,81], children in the
         reference's DFS order, parents' order kept; at least one level, >= target boards unless
@@ -455,3 +500,13 @@ class SudokuEngine:
         L.check(self.lib.sdk_solve_batch_dev(self.ctx, d_in.ptr, d_mask.ptr if d_mask else None, d_out.ptr,
                                              d_status.ptr, d_work.ptr if d_work else None, int(n)),
                 "sdk_solve_batch_dev")
+
+    def classify_batch_dev(self, d_in, d_out, d_status, n, budget=None):
+        L.check(self.lib.sdk_classify_batch_dev(self.ctx, d_in.ptr, d_out.ptr, d_status.ptr, int(n),
+                                                L.SDK_BUDGET_CONTEXT if budget is None else int(budget)),
+                "sdk_classify_batch_dev")
+
+    def minimize_batch_dev(self, d_in, d_order, d_out, d_status, n):
+        """The order rows are not validated on this path (see include/sudoku_hip.h)."""
+        L.check(self.lib.sdk_minimize_batch_dev(self.ctx, d_in.ptr, d_order.ptr, d_out.ptr, d_status.ptr, int(n)),
+                "sdk_minimize_batch_dev")

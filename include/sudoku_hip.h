@@ -42,7 +42,9 @@
 extern "C" {
 #endif
 
-#define SDK_ABI_VERSION 2   /* 2: sdk_solve_batch_ex, frontier records, p2p send/recv */
+#define SDK_ABI_VERSION 2   /* 2: sdk_solve_batch_ex, frontier records, p2p send/recv; version 2 */
+                            /* also gained sdk_classify_batch[_dev] and sdk_minimize_batch[_dev]  */
+                            /* (new symbols only: nothing a version-2 caller uses changed)        */
 
 /* return codes */
 #define SDK_OK        0
@@ -55,6 +57,7 @@ extern "C" {
 #define SDK_SOLVED        1   /* out = lexicographically first completion          */
 #define SDK_UNSOLVABLE    0   /* out = input (the reference restores the grid)     */
 #define SDK_BUDGET_HIT   -2   /* node budget exhausted; out = input                */
+#define SDK_MULTIPLE 2   /* classify only: at least two completions; out = input */
 
 /* check verdict bits (uint8_t) */
 #define SDK_CHECK_OK        1u  /* intended Sudoku.check(): all 27 units pass     */
@@ -215,6 +218,31 @@ int sdk_solve_batch_ex(sdk_ctx *ctx, const uint8_t *in, const uint16_t *first_ce
                        uint8_t *out, int8_t *status, uint64_t *work, size_t n, uint64_t node_budget,
                        int64_t donate);
 
+/* Uniqueness verdicts for n boards: does board i have no completion, exactly one, or several?
+ *   status  SDK_UNSOLVABLE (none), SDK_SOLVED (exactly one; out = that completion),
+ *           SDK_MULTIPLE (at least two) or SDK_BUDGET_HIT.
+ *   out     the input for every status but SDK_SOLVED.
+ * The constraint is the solver's and sdk_count_solutions' own (givens never conflict with
+ * givens, 10..255 are inert).  node_budget as in sdk_solve_batch_budget (SDK_BUDGET_CONTEXT =
+ * the context's SDK_OPT_NODE_BUDGET).  Always the QUAD kernel, in one launch after the
+ * propagation pass (SDK_OPT_PROP32*, as for a plain solve), whatever SDK_OPT_SOLVER,
+ * SDK_OPT_ORDER and SDK_OPT_DONATE say; it changes no option.  Any n up to 2^31-1 (batches
+ * above 2^24 boards run in slices of that many). */
+int sdk_classify_batch(sdk_ctx *ctx, const uint8_t *in, uint8_t *out, int8_t *status, size_t n,
+                       uint64_t node_budget);
+
+/* Greedy clue removal for n boards.  order is uint8[n][81]; row i is a permutation of 0..80, the
+ * cell order in which board i's clues are tried (anything else: SDK_EINVAL).  Per board:
+ *   status[i] = sdk_classify_batch's verdict of the input (no budget);
+ *   if it is not SDK_SOLVED, out[i] = the input; otherwise for q = 0..80 the cell order[i][q],
+ *   if non-zero, is cleared, and put back unless the board still has exactly one completion.
+ * out[i] is the result: a pure function of (board, order row), and a minimal puzzle (no clue
+ * can go) with the input's completion.  A "clue" is any non-zero cell; an inert given goes,
+ * because removing it changes no completion.  81 rounds of one streaming kernel and a classify
+ * launch each, enqueued without the host.  Any n up to 2^31-1 (slices of 2^24 boards). */
+int sdk_minimize_batch(sdk_ctx *ctx, const uint8_t *in, const uint8_t *order, uint8_t *out,
+                       int8_t *status, size_t n);
+
 /* The worklist step of a resumable lex-first search of a board whose solve hit the
  * budget (distributed_sudoku_solver_amd/search.py; the in-node form of handing a
  * subtree on, DHT_Node.py:491-510): expand n boards -- board i with first-cell mask
@@ -358,6 +386,14 @@ int sdk_synchronize(sdk_ctx *ctx);
 int sdk_check_batch_dev(sdk_ctx *ctx, const void *d_boards, void *d_verdict, size_t n);
 int sdk_solve_batch_dev(sdk_ctx *ctx, const void *d_in, const void *d_first_cell_mask,
                         void *d_out, void *d_status, void *d_work, size_t n);
+/* d_in and d_out 16-byte aligned, or the propagation pass is skipped */
+int sdk_classify_batch_dev(sdk_ctx *ctx, const void *d_in, void *d_out, void *d_status, size_t n,
+                           uint64_t node_budget);
+/* d_in and d_out 16-byte aligned (else SDK_EINVAL; d_out may be d_in).  The order rows are not
+ * validated here: an entry >= 81 is "no cell" (that round leaves the board unchanged), and a
+ * repeated cell is tried again (a no-op: it is empty, or it could not go). */
+int sdk_minimize_batch_dev(sdk_ctx *ctx, const void *d_in, const void *d_order, void *d_out,
+                           void *d_status, size_t n);
 
 /* Kernel time accounting (HIP events on the context stream, bracketing every
  * kernel launched by the *_dev / host calls since the last reset).  Only with
