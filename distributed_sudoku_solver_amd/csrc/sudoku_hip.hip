@@ -11,6 +11,7 @@
 #include <cstddef>
 #include <cstdio>
 #include <cstring>
+#include <initializer_list>
 #include <mutex>
 #include <new>
 #include <string>
@@ -92,16 +93,18 @@ struct DevBuf {
     }
 };
 
-// A host-pointer call that staged through the pinned area: an error return may leave copies
-// from / into it queued, so drain the stream first -- the next call's memcpy into the area (or a
-// grow that frees it) cannot race them.  Disarmed once the call has synchronized.
-struct DrainOnError {
-    hipStream_t s;
-    bool armed;
-    ~DrainOnError() {
-        if (armed) (void)hipStreamSynchronize(s);
-    }
-};
+// argument checks the host-pointer and _dev forms of a call share
+int check_budget_arg(uint64_t node_budget) {
+    if (node_budget != SDK_BUDGET_CONTEXT && node_budget > (uint64_t)INT64_MAX)
+        return fail(SDK_EINVAL, "node budget out of range");
+    return SDK_OK;
+}
+int check_board_count(size_t n) {
+    if (n > 0x7FFFFFFFull) return fail(SDK_EINVAL, "at most 2^31-1 boards per call");
+    return SDK_OK;
+}
+// an ABI node budget as a SolveCall's: SDK_BUDGET_CONTEXT is "the context's"
+int64_t budget_arg(uint64_t node_budget) { return node_budget == SDK_BUDGET_CONTEXT ? -1 : (int64_t)node_budget; }
 
 }  // namespace
 
@@ -302,7 +305,7 @@ __global__ void dn_scatter_kernel(const uint32_t* list, const uint8_t* sub_out, 
 }
 }  // namespace sdk
 
-// Pinned host staging of the host-pointer calls (sdk_solve_batch_ex, sdk_expand_boards): the
+// Pinned host staging of the host-pointer calls (Staging below): the
 // caller's arrays are copied into it on the CPU and moved by true asynchronous DMA.  HIP's own path
 // for pageable memory took 12-25 ms per call now and then for a 1.3 MB transfer whose kernel ran
 // 0.2 ms (profiles/r05/slice_probe_timing_r05c.log: a node's search slices), all of it CPU time in
@@ -314,6 +317,12 @@ struct HostBuf {
 constexpr size_t kStageMax = size_t(256) << 20;
 constexpr size_t kStageInit = size_t(8) << 20;   // allocated with the context: pinning costs ~ms
                                                  // (the first slice of a node paid 34 ms growing it)
+
+// The boards one phase of a phased solve passes to the next, as a dense batch: their list (length
+// word first, then their indices), their inputs and first-cell masks, and the donation launch's answers.
+struct DnTail {
+    DevBuf list, in, mask, out, st, work;
+};
 
 struct sdk_ctx {
     int device = 0;
@@ -340,25 +349,24 @@ struct sdk_ctx {
     int donate = 1;                // QUAD, LEX solves: subtree donation (SDK_OPT_DONATE)
     DevBuf dn;                     // two donation areas (solve4_kernel.h: DnCtl, records, items,
                                    // mailboxes), one per donation phase of a phased solve
-    void* dn_area = nullptr;       // the area of the donation launch being enqueued
-    DevBuf dn_in, dn_mask, dn_out, dn_st, dn_work, dn_list;        // the phased solve's tail boards
-    DevBuf dn3_in, dn3_mask, dn3_out, dn3_st, dn3_work, dn3_list;   // ... and its LEX re-solves
+    DnTail dn_tail[2];             // [0] the phased solve's tail boards (area 0), [1] its LEX re-solves (area 1)
     DevBuf dn_stat;                // [0] boards the last phased solve passed to the donation
                                    // kernel, [1] of those, boards re-solved in LEX order
+    // The last solve's outcome, read by later ABI calls (sdk_get_option, sdk_debug_p32_list,
+    // dn_check_error) -- everything else about a call travels in its SolveCall.  A classify is a
+    // one-launch solve: dn_ran is false after it, and prop32_ran is that of its last slice.  A
+    // prop32 fallback solve (n_dev set) leaves prop32_ran alone.
     bool dn_ran = false;           // the last solve was phased (dn_stat and `delivered` are its)
-    bool timer_hold = false;       // a phased solve is being timed as one span
+    bool prop32_ran = false;       // the last solve ran the prop32 pass (p32_list[0] = its undecided boards)
     bool dn_err_check = false;     // a phased solve ran since its control blocks' error words were read
     int dn_fault = 0;              // SDK_OPT_DN_FAULT (test only)
     int dn_helpers = 2;            // SDK_OPT_DONATE_HELPERS: donation-launch waves per listed board (+ 64)
     int dn_resume = 1;             // SDK_OPT_DONATE_RESUME: split boards resume from their saved stacks
-    bool dn_resume_now = false;    // ... in the phased solve being enqueued (launch_solve)
     DevBuf dn_save, dn_save_idx, dn_seeds;   // sdk::SplitSave, its entry per board, the seed list
     int dn_exhaustive = 1;         // phase 2 in MRV count-to-2 order (SDK_OPT_DONATE_MODE)
     int64_t dn_max = 1 << 19;      // largest batch solved in phases (SDK_OPT_DONATE_MAX, 0 = any)
     uint32_t dn_epoch = 0;         // launches that used it (mailbox / registration entries carry it)
     int dn_blocks_per_cu = 0;      // resident solve4_kernel<true> workgroups per CU (queried once)
-    uint64_t split_big = 0;        // the phased solve being enqueued: its split budget above
-                                   // sdk::kBudgetBigBoards searched boards (device-counted batches)
     int prop32 = 1;                // QUAD: bit-sliced root propagation first (SDK_OPT_PROP32)
     int prop32_lc = 5 | (3 << 8);  // ... a locked-candidates pass every this many steps (low byte),
                                    //     the first after step (value >> 8), 0 = the period: after
@@ -367,7 +375,6 @@ struct sdk_ctx {
     int prop32_handover = 1;       // ... undecided boards searched from their propagated grids
     int prop32_tail_live = 0;      // ... a group's last (at most this many) live boards handed over
     int prop32_tail_step = 24;     //     from this step on (SDK_OPT_PROP32_TAIL = live | step << 8)
-    bool prop32_ran = false;       // the last solve ran it (p32_list[0] = its undecided boards)
     DevBuf p32_ctl, p32_list, p32_in, p32_out, p32_st;
     int clock_probe = 0;           // sdk_debug_clock_arm: prop32 passes run the stamped twin
     DevBuf p32_stamps;             // ... its stamps, 4 words per workgroup of the last such pass
@@ -382,13 +389,13 @@ struct sdk_ctx {
     uint32_t fr_levels = 0;
     bool fr_valid = false;
     int fr_mode = SDK_FRONTIER_COUNT;   // kept by refinements and loaded records
-    long long* first_found = nullptr;   // set by frontier_first for its solve launch (SolveArgs::found)
     // RCCL communicator (sdk_comm_init), one rank per context
     ncclComm_t comm = nullptr;
     int comm_rank = 0;
     int comm_world = 1;
     // timing
     bool timing = false;          // SDK_OPT_TIMING
+    bool timer_hold = false;      // a TimedSpan is open: the launches inside it are not timed apart
     std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
     size_t events_used = 0;
 };
@@ -450,11 +457,131 @@ int timer_end(sdk_ctx* c, hipEvent_t stop) {
     return SDK_OK;
 }
 
+// Several launches timed as ONE span (a phased solve, the prop32 fallback, a minimise call): begin()
+// records the start and holds the timer, so the launches and spans inside record nothing; end(rc)
+// records the stop when the work returned SDK_OK.  The hold goes back to what it was on every path
+// out of the scope (under an outer span the whole object does nothing).
+struct TimedSpan {
+    sdk_ctx* c;
+    const bool outer;
+    hipEvent_t stop = nullptr;
+    explicit TimedSpan(sdk_ctx* ctx) : c(ctx), outer(ctx->timer_hold) {}
+    ~TimedSpan() { c->timer_hold = outer; }
+    int begin() {
+        const int rc = timer_begin(c, &stop);
+        if (!rc) c->timer_hold = true;
+        return rc;
+    }
+    int end(int rc) {
+        c->timer_hold = outer;
+        return rc ? rc : timer_end(c, stop);
+    }
+};
+
+// a grid for `items` at `per_block` each: at least one block, at most `blocks_per_cu` per CU
+unsigned grid_for(const sdk_ctx* c, uint64_t items, uint64_t per_block, uint64_t blocks_per_cu) {
+    return (unsigned)std::max<uint64_t>(
+        1, std::min<uint64_t>((items + per_block - 1) / per_block, (uint64_t)c->cus * blocks_per_cu));
+}
+
+// One slot of a host-pointer call's staging: `bytes` that go from the caller's `h_src` to the device
+// (`d_dst`) before the launch, come back from `d_src` to the caller's `h_dst` after it, or both through
+// the same slot.  A null host pointer leaves that copy out; the slot keeps its place.
+struct Piece {
+    size_t bytes;
+    const void* h_src;
+    void* d_dst;
+    const void* d_src = nullptr;
+    void* h_dst = nullptr;
+    char* slot = nullptr;   // (Staging's: its place in the pinned area)
+};
+
+// The copies of a host-pointer call: send() before the launch, fetch() after it (it synchronizes).
+// The (at most four) pieces lie in the pinned area (HostBuf) in the order given -- widest element
+// type first, so every slot is aligned for its type; a call too large for the area copies straight
+// from / to the caller's pageable memory.  An error return between send() and the end of fetch()
+// may leave copies from / into the area queued, so the stream is drained first: the next call's
+// memcpy into the area (or a grow that frees it) cannot race them.
+class Staging {
+    sdk_ctx* c;
+    Piece p[4];
+    int np = 0;
+    bool armed = true;
+
+  public:
+    Staging(sdk_ctx* ctx, std::initializer_list<Piece> pieces) : c(ctx) {
+        size_t total = 0;
+        for (const Piece& q : pieces) {
+            p[np++] = q;
+            total += q.bytes;
+        }
+        char* st = static_cast<char*>(stage_host(c->stage, total));
+        for (int i = 0; i < np && st; ++i) {
+            p[i].slot = st;
+            st += p[i].bytes;
+        }
+    }
+    ~Staging() {
+        if (armed) (void)hipStreamSynchronize(c->stream);
+    }
+    int send() {
+        for (int i = 0; i < np; ++i)
+            if (p[i].h_src && p[i].slot) std::memcpy(p[i].slot, p[i].h_src, p[i].bytes);
+        for (int i = 0; i < np; ++i)
+            if (p[i].h_src)
+                HIPCALL(hipMemcpyAsync(p[i].d_dst, p[i].slot ? p[i].slot : p[i].h_src, p[i].bytes,
+                                       hipMemcpyHostToDevice, c->stream));
+        return SDK_OK;
+    }
+    int fetch() {
+        for (int i = 0; i < np; ++i)
+            if (p[i].h_dst)
+                HIPCALL(hipMemcpyAsync(p[i].slot ? p[i].slot : p[i].h_dst, p[i].d_src, p[i].bytes,
+                                       hipMemcpyDeviceToHost, c->stream));
+        HIPCALL(hipStreamSynchronize(c->stream));
+        armed = false;
+        for (int i = 0; i < np; ++i)
+            if (p[i].h_dst && p[i].slot) std::memcpy(p[i].h_dst, p[i].slot, p[i].bytes);
+        return SDK_OK;
+    }
+};
+
+// One solve's arguments (launch_solve).  A call site gives the buffers and the board count, in this
+// order (each of its own type), and names whatever else it sets.
+struct SolveCall {
+    const uint8_t* in = nullptr;        // boards in_first, in_first + in_step, ... of `in`
+    const uint16_t* mask = nullptr;     // first-cell masks (nullable)
+    uint8_t* out = nullptr;
+    int8_t* status = nullptr;
+    uint64_t* work = nullptr;           // work counters (nullable)
+    size_t n = 0;
+    const uint32_t* n_dev = nullptr;    // the batch's length on the device (n bounds it; the prop32 fallback)
+    uint64_t in_first = 0, in_step = 1;
+    int count_mode = 0;                 // count completions (up to `limit`) into *count / counts[i]
+    uint64_t limit = 0;
+    unsigned long long* count = nullptr;
+    unsigned long long* counts = nullptr;
+    int order = -1;                     // SDK_ORDER_* or sdk::ORDER_CLASSIFY; -1 = the context's
+    int64_t budget = -1;                // search nodes per board, 0 = unlimited; -1 = the context's
+    int64_t donate = -1;                // SDK_OPT_DONATE for this call; -1 = the context's
+    int solver = -1;                    // SDK_SOLVER_*; -1 = the context's
+    long long* found = nullptr;         // a first-solution scan's found word (frontier_first; SolveArgs::found)
+};
+
+// What one launch of a phased solve adds to its SolveCall (launch_solve_once).
+struct SolvePhase {
+    enum Kind { kPlain, kSplit, kDonation };
+    Kind kind = kPlain;
+    void* area = nullptr;               // kDonation: the donation area
+    uint64_t budget_big = 0;            // kSplit: the budget above sdk::kBudgetBigBoards searched boards
+    bool save = false;                  // kSplit: the stacks of stopped boards are saved for resume
+};
+
 int launch_check(sdk_ctx* c, const uint8_t* d_in, uint8_t* d_out, size_t n) {
     if (n == 0) return SDK_OK;
     if (reinterpret_cast<uintptr_t>(d_in) & 15) return fail(SDK_EINVAL, "device boards must be 16-byte aligned");
     const uint64_t tiles = (n + sdk::kCheckThreads - 1) / sdk::kCheckThreads;
-    const unsigned grid = (unsigned)std::min<uint64_t>(tiles, (uint64_t)c->cus * c->check_blocks_per_cu);
+    const unsigned grid = grid_for(c, n, sdk::kCheckThreads, c->check_blocks_per_cu);
     hipEvent_t stop;
     int rc = timer_begin(c, &stop);
     if (rc) return rc;
@@ -474,45 +601,40 @@ int launch_check(sdk_ctx* c, const uint8_t* d_in, uint8_t* d_out, size_t n) {
     return SDK_OK;
 }
 
-
-// dn_phase (QUAD, LEX solves with SDK_OPT_DONATE): 0 plain launch; 1 the split phase (plain
-// kernel, split budget); 2 the donation kernel solve4_kernel<true> on the full resident grid,
-// donation area c->dn_area (see launch_solve).  The phases' control words are zeroed by
-// launch_solve's prep launch.
-int launch_solve_once(sdk_ctx* c, const uint8_t* d_in, const uint16_t* d_mask, uint8_t* d_out, int8_t* d_status,
-                      uint64_t* d_work, size_t n, int count_mode, uint64_t limit, unsigned long long* d_count,
-                      unsigned long long* d_counts, uint64_t in_first, uint64_t in_step, int order, int64_t budget,
-                      int dn_phase, const uint32_t* n_dev = nullptr) {
-    // budget: node budget per board for this launch (-1 = the context's SDK_OPT_NODE_BUDGET)
-    const uint64_t node_budget = budget >= 0 ? (uint64_t)budget : c->budget;
+// One solve kernel launch.  `s` is a call launch_solve has resolved (order, budget and solver are
+// values, not -1); `ph` says which launch of a phased solve (QUAD, LEX or MRV_UNIQUE solves with
+// SDK_OPT_DONATE) it is: the plain launch; the split phase (plain kernel, s.budget = the split budget);
+// or the donation kernel solve4_kernel<true> on the full resident grid, in donation area ph.area
+// (see launch_solve).  The phases' control words are zeroed by launch_solve's prep launch.
+int launch_solve_once(sdk_ctx* c, const SolveCall& s, const SolvePhase& ph = {}) {
+    const size_t n = s.n;
+    const int count_mode = s.count_mode;
+    const bool plain = ph.kind == SolvePhase::kPlain, donation = ph.kind == SolvePhase::kDonation;
     if (n == 0) return SDK_OK;
-    if (n > 0x7FFFFFFFull) return fail(SDK_EINVAL, "at most 2^31-1 boards per call");
-    if (c->solver == SDK_SOLVER_LANE && !count_mode) {
+    int rc;
+    if ((rc = check_board_count(n))) return rc;
+    sdk::SolveArgs a{};   // what every solve kernel takes from the call; the rest is set below
+    a.in = s.in;
+    a.mask = s.mask;
+    a.out = s.out;
+    a.status = s.status;
+    a.work = s.work;
+    a.n = n;
+    a.budget = (uint64_t)s.budget;
+    a.in_first = s.in_first;
+    a.in_step = s.in_step;
+    hipEvent_t stop;
+    if (s.solver == SDK_SOLVER_LANE && !count_mode) {
         // one board per lane: the reference's own DFS (solve_lane_kernel.h); `work` =
         // the reference's validations, the budget counts validations
-        if (!d_out || !d_status) return fail(SDK_EINVAL, "solve needs out and status buffers");
-        if (order == SDK_ORDER_MRV_UNIQUE || (order < 0 && c->order == SDK_ORDER_MRV_UNIQUE))
+        if (!s.out || !s.status) return fail(SDK_EINVAL, "solve needs out and status buffers");
+        if (s.order == SDK_ORDER_MRV_UNIQUE)
             return fail(SDK_EINVAL, "the LANE solver runs the reference's order only (SDK_ORDER_LEX)");
-        int rc = ensure(c->counter, 256);
-        if (rc) return rc;
+        if ((rc = ensure(c->counter, 256))) return rc;
         HIPCALL(hipMemsetAsync(c->counter.p, 0, 8, c->stream));
-        sdk::SolveArgs a{};
-        a.in = d_in;
-        a.mask = d_mask;
-        a.out = d_out;
-        a.status = d_status;
-        a.work = d_work;
-        a.n = n;
         a.next = static_cast<uint32_t*>(c->counter.p);
-        a.budget = node_budget;
-        a.in_first = in_first;
-        a.in_step = in_step;
-        const uint64_t blocks = (n + sdk::kLaneThreads - 1) / sdk::kLaneThreads;
-        const unsigned grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(blocks, (uint64_t)c->cus * 6));
-        hipEvent_t stop;
-        rc = timer_begin(c, &stop);
-        if (rc) return rc;
-        sdk::solve_lane_kernel<<<grid, sdk::kLaneThreads, 0, c->stream>>>(a);
+        if ((rc = timer_begin(c, &stop))) return rc;
+        sdk::solve_lane_kernel<<<grid_for(c, n, sdk::kLaneThreads, 6), sdk::kLaneThreads, 0, c->stream>>>(a);
         HIPCALL(hipGetLastError());
         return timer_end(c, stop);
     }
@@ -520,11 +642,11 @@ int launch_solve_once(sdk_ctx* c, const uint8_t* d_in, const uint16_t* d_mask, u
     // one board per wave
     // count mode: QUAD counts four boards per wave (solve4's count mode) unless per-board counts
     // are asked for; the other solvers count with the one-board-per-wave kernel
-    const int per_wave = count_mode ? ((c->solver == SDK_SOLVER_QUAD && !d_counts) ? 4 : 1)
-                                    : (c->solver == SDK_SOLVER_QUAD ? 4 : (c->solver == SDK_SOLVER_HALFWAVE ? 2 : 1));
+    const int per_wave = count_mode ? ((s.solver == SDK_SOLVER_QUAD && !s.counts) ? 4 : 1)
+                                    : (s.solver == SDK_SOLVER_QUAD ? 4 : (s.solver == SDK_SOLVER_HALFWAVE ? 2 : 1));
     const bool two = per_wave == 2, four = per_wave == 4;
-    if ((two || four) && !d_status) return fail(SDK_EINVAL, "solve needs a status buffer");
-    if ((two || four) && !count_mode && !d_out) return fail(SDK_EINVAL, "solve needs an out buffer");
+    if ((two || four) && !s.status) return fail(SDK_EINVAL, "solve needs a status buffer");
+    if ((two || four) && !count_mode && !s.out) return fail(SDK_EINVAL, "solve needs an out buffer");
     const uint64_t slots = (uint64_t)c->cus * (per_wave > 1 ? c->waves_per_cu2 : c->waves_per_cu) * per_wave;
     // 16 boards per dequeue (fewer when a slot would get < 2 dequeues); 8 for the QUAD solver,
     // whose dequeues go to per-XCD heads with one stage per wave and dealt first chunks: there
@@ -541,67 +663,51 @@ int launch_solve_once(sdk_ctx* c, const uint8_t* d_in, const uint16_t* d_mask, u
         : c->solve_chunk ? (uint32_t)c->solve_chunk
         : (uint32_t)std::min<uint64_t>(per_wave == 4 ? quad_chunk : 16, std::max<uint64_t>(1, n / (slots * 2)));
     const uint64_t want = (n + chunk - 1) / chunk;
-    const unsigned grid = (unsigned)std::max<uint64_t>(
-        1, std::min<uint64_t>((want + per_wave - 1) / per_wave, slots / per_wave));
+    const unsigned grid = grid_for(c, want, per_wave, per_wave > 1 ? c->waves_per_cu2 : c->waves_per_cu);
     const size_t stack_words = four ? sdk::kStack4WordsPerBlock : (two ? sdk::kStack2WordsPerBlock : sdk::kStackWordsPerBlock);
-    int rc = ensure(c->stack, (size_t)grid * stack_words * sizeof(uint32_t));
-    if (rc) return rc;
-    rc = ensure(c->counter, 256);
-    if (rc) return rc;
+    if ((rc = ensure(c->stack, (size_t)grid * stack_words * sizeof(uint32_t))) || (rc = ensure(c->counter, 256)))
+        return rc;
     // QUAD with per-XCD heads: the dequeue counter lives in the heads region after the heads.
     // Plain launches take a fresh region of a pool of kHeadRounds, cleared by one memset every
     // kHeadRounds launches (a per-launch memset is its own ~4 us dispatch in front of the
     // kernel); the split phase's region is cleared by its prep launch.  Otherwise the counter
     // is word 0 of c->counter (words 1.. belong to callers).
-    const bool use_heads = four && c->xcd_heads && dn_phase != 2;
+    const bool use_heads = four && c->xcd_heads && !donation;
     uint32_t* heads = nullptr;
     if (use_heads) {
         if ((rc = ensure(c->heads, (size_t)kHeadRounds * sdk::kHeadWords * sizeof(uint32_t)))) return rc;
         uint32_t region = 0;
-        if (dn_phase == 0) {
+        if (plain) {
             region = c->heads_round++ % kHeadRounds;
             if (region == 0)
                 HIPCALL(hipMemsetAsync(c->heads.p, 0, (size_t)kHeadRounds * sdk::kHeadWords * sizeof(uint32_t), c->stream));
         }
         heads = static_cast<uint32_t*>(c->heads.p) + (size_t)region * sdk::kHeadWords;
-    } else if (dn_phase == 0) {
+    } else if (plain) {
         HIPCALL(hipMemsetAsync(c->counter.p, 0, 8, c->stream));
     }
-    sdk::SolveArgs a;
-    a.in = d_in;
-    a.mask = d_mask;
-    a.out = d_out;
-    a.status = d_status;
-    a.work = d_work;
-    a.n = n;
     a.next = use_heads ? heads + sdk::kHeadNext : static_cast<uint32_t*>(c->counter.p);
+    a.heads = heads;
     a.stack = static_cast<uint32_t*>(c->stack.p);
-    a.budget = node_budget;
-    a.order = order >= 0 ? order : c->order;
-    a.limit = limit;
-    a.count = d_count;
-    a.counts = d_counts;
+    a.order = s.order;
+    a.limit = s.limit;
+    a.count = s.count;
+    a.counts = s.counts;
     a.count_mode = count_mode;
     a.chunk = chunk;
     a.work_rounds = c->work_rounds;
-    a.in_first = in_first;
-    a.in_step = in_step;
     a.locked = c->locked;
-    a.heads = nullptr;
-    a.donate = nullptr;
-    a.n_dev = n_dev;   // the plain and split launches of a prop32 fallback: the list's length
-    a.save = nullptr;
-    a.save_idx = nullptr;
+    a.n_dev = s.n_dev;   // the plain and split launches of a prop32 fallback: the list's length
     // a first-solution scan (frontier_first): the plain QUAD launch cancels boards above the lowest hit
-    a.found = (four && !count_mode && dn_phase == 0) ? c->first_found : nullptr;
-    a.budget_big = (four && dn_phase == 1) ? c->split_big : 0;   // the split phase of a device-counted batch
-    if (dn_phase == 1 && c->dn_resume_now && four && !count_mode) {
+    if (four && !count_mode && plain) a.found = s.found;
+    if (four && ph.kind == SolvePhase::kSplit) a.budget_big = ph.budget_big;   // (a device-counted batch)
+    if (ph.kind == SolvePhase::kSplit && ph.save && four && !count_mode) {
         // the split phase leaves the stacks of the boards it stops (sdk::split_save4)
         a.save = c->dn_save.p;
         a.save_idx = static_cast<uint32_t*>(c->dn_save_idx.p);
     }
     unsigned grid_used = grid;
-    if (four && !count_mode && dn_phase == 2) {
+    if (four && !count_mode && donation) {
         // subtree donation: idle waves wait for items while any wave of the grid works, so the
         // grid is the resident one (its occupancy, not waves_per_cu2), whatever the batch size:
         // waves without a board of their own are the helpers
@@ -609,12 +715,11 @@ int launch_solve_once(sdk_ctx* c, const uint8_t* d_in, const uint16_t* d_mask, u
             c->dn_blocks_per_cu = sdk::solve4_dn_blocks_per_cu();
             if (c->dn_blocks_per_cu <= 0) return fail(SDK_EHIP, "occupancy query for the donation kernel failed");
         }
-        a.donate = c->dn_area;
-        // the boards: a list length on the device (n bounds it), one per dequeue on the
+        a.donate = ph.area;
+        // the boards: a list length on the device (s.n_dev; n bounds it), one per dequeue on the
         // area's own counter
-        a.n_dev = n_dev;
         a.chunk = 1;
-        a.next = &static_cast<sdk::DnCtl*>(c->dn_area)->next;
+        a.next = &static_cast<sdk::DnCtl*>(ph.area)->next;
         // the resident grid, at most what the kernel keeps of it for n boards: n / 4 + 64 + helpers x
         // min(n, kDnHelpCap) (solve4_kernel; the list on the device may be shorter, then it keeps less)
         grid_used = (unsigned)std::max<uint64_t>(
@@ -623,15 +728,11 @@ int launch_solve_once(sdk_ctx* c, const uint8_t* d_in, const uint16_t* d_mask, u
                                    ((uint64_t)n + 3) / 4 + 64ull +
                                        (uint64_t)c->dn_helpers * std::min<uint64_t>(n, sdk::kDnHelpCap)}));
         if (grid_used > grid) {
-            rc = ensure(c->stack, (size_t)grid_used * stack_words * sizeof(uint32_t));
-            if (rc) return rc;
+            if ((rc = ensure(c->stack, (size_t)grid_used * stack_words * sizeof(uint32_t)))) return rc;
             a.stack = static_cast<uint32_t*>(c->stack.p);
         }
     }
-    if (use_heads) a.heads = heads;
-    hipEvent_t stop;
-    rc = timer_begin(c, &stop);
-    if (rc) return rc;
+    if ((rc = timer_begin(c, &stop))) return rc;
     if (four) {
         HIPCALL(sdk::launch_solve4(a, grid_used, c->stream));
     } else if (two) {
@@ -640,8 +741,7 @@ int launch_solve_once(sdk_ctx* c, const uint8_t* d_in, const uint16_t* d_mask, u
         sdk::solve_kernel<<<grid, 64, 0, c->stream>>>(a);
     }
     HIPCALL(hipGetLastError());
-    if ((rc = timer_end(c, stop))) return rc;
-    return SDK_OK;
+    return timer_end(c, stop);
 }
 
 // Solve launch.  QUAD solves with SDK_OPT_DONATE (LEX, or MRV_UNIQUE: its split phase counts to
@@ -664,15 +764,15 @@ int launch_solve_once(sdk_ctx* c, const uint8_t* d_in, const uint16_t* d_mask, u
 // phased pass; larger calls run in passes of that many.
 constexpr uint64_t kDnCapBoards = 1ull << 24;
 
-// list the boards of status[0, n) (n bounded by *n_dev when given) that carry `code` into
-// `list` (its length zeroed by the prep launch), copying them to (buf_in, buf_mask)
+// List the boards of `from` (its statuses [0, n), n bounded by *n_dev when given) that carry `code`
+// into tail `k`'s list (its length zeroed by the prep launch; k also numbers its dn_stat word and its
+// donation area), copying their inputs and masks to the tail's dense batch.
 // resume: the split phase's list -- boards with saved stacks go to the seed list, and
 // dn_seed_kernel lists them after the restarted ones (donation area 0)
-int dn_collect(sdk_ctx* c, const int8_t* d_status, uint64_t n, const uint32_t* n_dev, int8_t code, DevBuf& list,
-               int stat, const uint8_t* d_in, const uint16_t* d_mask, uint64_t in_first, uint64_t in_step,
-               DevBuf& buf_in, DevBuf& buf_mask, bool resume = false) {
+int dn_collect(sdk_ctx* c, const SolveCall& from, int8_t code, int k, bool resume) {
+    DnTail& t = c->dn_tail[k];
     int rc;
-    if ((rc = ensure(buf_in, (size_t)n * 81)) || (d_mask && (rc = ensure(buf_mask, (size_t)n * 2)))) return rc;
+    if ((rc = ensure(t.in, from.n * 81)) || (from.mask && (rc = ensure(t.mask, from.n * 2)))) return rc;
     sdk::DnResume rs{};
     if (resume) {
         rs.save = static_cast<const sdk::SplitSave*>(c->dn_save.p);
@@ -680,60 +780,57 @@ int dn_collect(sdk_ctx* c, const int8_t* d_status, uint64_t n, const uint32_t* n
         rs.ctl = static_cast<sdk::DnCtl*>(c->dn.p);
         rs.seeds = static_cast<uint32_t*>(c->dn_seeds.p);
     }
-    uint32_t* lst = static_cast<uint32_t*>(list.p);
-    uint32_t* total = static_cast<uint32_t*>(c->dn_stat.p) + stat;
-    uint8_t* bin = static_cast<uint8_t*>(buf_in.p);
-    uint16_t* bmask = static_cast<uint16_t*>(d_mask ? buf_mask.p : nullptr);
-    sdk::dn_collect_kernel<<<(unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n + 255) / 256, (uint64_t)c->cus * 8)),
-                             256, 0, c->stream>>>(d_status, n, n_dev, code, lst, total, d_in, d_mask, in_first, in_step,
-                                                  bin, bmask, rs);
+    uint32_t* lst = static_cast<uint32_t*>(t.list.p);
+    uint32_t* total = static_cast<uint32_t*>(c->dn_stat.p) + k;
+    uint8_t* bin = static_cast<uint8_t*>(t.in.p);
+    uint16_t* bmask = static_cast<uint16_t*>(from.mask ? t.mask.p : nullptr);
+    sdk::dn_collect_kernel<<<grid_for(c, from.n, 256, 8), 256, 0, c->stream>>>(
+        from.status, from.n, from.n_dev, code, lst, total, from.in, from.mask, from.in_first, from.in_step, bin, bmask,
+        rs);
     HIPCALL(hipGetLastError());
     if (resume) {
-        sdk::dn_seed_kernel<<<(unsigned)std::min<uint64_t>(sdk::kSeedBoards, (uint64_t)c->cus * 4), 64, 0, c->stream>>>(
-            rs.seeds, rs.save, lst, total, d_in, d_mask, in_first, in_step, bin, bmask, rs.ctl);
+        sdk::dn_seed_kernel<<<grid_for(c, sdk::kSeedBoards, 1, 4), 64, 0, c->stream>>>(
+            rs.seeds, rs.save, lst, total, from.in, from.mask, from.in_first, from.in_step, bin, bmask, rs.ctl);
         HIPCALL(hipGetLastError());
     }
     return SDK_OK;
 }
 
-// solve the (at most cap) boards `list` collected into buf_in/buf_mask with the donation
-// kernel (order) in donation area `area`, scatter the answers into (d_out, d_status, d_work)
-// (n_dev: the boards the donation launch dequeues -- the list's length, or with resumed boards
-// the restarted ones alone)
-int dn_resolve(sdk_ctx* c, uint64_t cap, const DevBuf& list, int area, bool has_mask, uint8_t* d_out,
-               int8_t* d_status, uint64_t* d_work, int order, int64_t budget, DevBuf& buf_in, DevBuf& buf_mask,
-               DevBuf& buf_out, DevBuf& buf_st, DevBuf& buf_work, const uint32_t* n_dev = nullptr) {
+// Solve the (at most to.n) boards dn_collect listed in tail `k` with the donation kernel (`order`,
+// to's budget) in donation area k, and scatter the answers into to's out, status and work.
+// dequeue: the boards the donation launch dequeues when that is not the list's length (with
+// resumed boards, the restarted ones alone).
+int dn_resolve(sdk_ctx* c, const SolveCall& to, int k, int order, const uint32_t* dequeue = nullptr) {
+    DnTail& t = c->dn_tail[k];
     int rc;
-    if ((rc = ensure(buf_out, (size_t)cap * 81)) || (rc = ensure(buf_st, cap)) ||
-        (d_work && (rc = ensure(buf_work, (size_t)cap * 8))))
+    if ((rc = ensure(t.out, to.n * 81)) || (rc = ensure(t.st, to.n)) || (to.work && (rc = ensure(t.work, to.n * 8))))
         return rc;
-    const uint32_t* lst = static_cast<const uint32_t*>(list.p);
-    uint8_t* in = static_cast<uint8_t*>(buf_in.p);
-    uint16_t* mask = has_mask ? static_cast<uint16_t*>(buf_mask.p) : nullptr;
-    uint8_t* out = static_cast<uint8_t*>(buf_out.p);
-    int8_t* st = static_cast<int8_t*>(buf_st.p);
-    uint64_t* work = d_work ? static_cast<uint64_t*>(buf_work.p) : nullptr;
-    c->dn_area = static_cast<char*>(c->dn.p) + (size_t)area * sdk::kDnBytes;
-    if ((rc = launch_solve_once(c, in, mask, out, st, work, cap, 0, 0, nullptr, nullptr, 0, 1, order, budget, 2,
-                                n_dev ? n_dev : lst)))
-        return rc;
+    const uint32_t* lst = static_cast<const uint32_t*>(t.list.p);
+    SolveCall sub{static_cast<uint8_t*>(t.in.p), to.mask ? static_cast<uint16_t*>(t.mask.p) : nullptr,
+                  static_cast<uint8_t*>(t.out.p), static_cast<int8_t*>(t.st.p),
+                  to.work ? static_cast<uint64_t*>(t.work.p) : nullptr, to.n};
+    sub.n_dev = dequeue ? dequeue : lst;
+    sub.order = order;
+    sub.budget = to.budget;
+    sub.solver = to.solver;
+    const SolvePhase ph{SolvePhase::kDonation, static_cast<char*>(c->dn.p) + (size_t)k * sdk::kDnBytes};
+    if ((rc = launch_solve_once(c, sub, ph))) return rc;
     if (order == SDK_ORDER_MRV_UNIQUE) {
         // boards with several completions (or undecided): LEX order, donation again
-        if ((rc = dn_collect(c, st, cap, lst, (int8_t)sdk::kDnRetryLex, c->dn3_list, 1, in, mask, 0, 1, c->dn3_in,
-                             c->dn3_mask)) ||
-            (rc = dn_resolve(c, cap, c->dn3_list, 1, has_mask, out, st, work, SDK_ORDER_LEX, budget, c->dn3_in,
-                             c->dn3_mask, c->dn3_out, c->dn3_st, c->dn3_work)))
+        sub.n_dev = lst;
+        if ((rc = dn_collect(c, sub, (int8_t)sdk::kDnRetryLex, 1, false)) ||
+            (rc = dn_resolve(c, sub, 1, SDK_ORDER_LEX)))
             return rc;
     }
-    const unsigned g = (unsigned)std::min<uint64_t>(cap, (uint64_t)c->cus * 16);
-    sdk::dn_scatter_kernel<<<g, 128, 0, c->stream>>>(lst, out, st, work, c->work_rounds == SDK_WORK_DEPTH, d_out,
-                                                     d_status, d_work);
+    sdk::dn_scatter_kernel<<<grid_for(c, to.n, 1, 16), 128, 0, c->stream>>>(
+        lst, sub.out, sub.status, sub.work, c->work_rounds == SDK_WORK_DEPTH, to.out, to.status, to.work);
     HIPCALL(hipGetLastError());
     return SDK_OK;
 }
 
 // zero a phased pass's control words in one launch (sdk::dn_prep_kernel)
-int dn_prep(sdk_ctx* c, uint64_t cap, bool first_pass) {
+// resume: the pass saves the split phase's stacks (their buffers are sized and zeroed too)
+int dn_prep(sdk_ctx* c, uint64_t cap, bool first_pass, bool resume) {
     int rc;
     if (c->dn.bytes < 2 * sdk::kDnBytes || c->dn_epoch > 0xFFFFFF00u) {
         // entries of epoch 0 (and, after 2^32 launches, the stale ones cleared once)
@@ -743,7 +840,8 @@ int dn_prep(sdk_ctx* c, uint64_t cap, bool first_pass) {
     }
     if ((rc = ensure(c->dn_stat, 256)) || (rc = ensure(c->counter, 256)) ||
         (rc = ensure(c->heads, (size_t)kHeadRounds * sdk::kHeadWords * sizeof(uint32_t))) ||
-        (rc = ensure(c->dn_list, (cap + 1) * sizeof(uint32_t))) || (rc = ensure(c->dn3_list, (cap + 1) * sizeof(uint32_t))))
+        (rc = ensure(c->dn_tail[0].list, (cap + 1) * sizeof(uint32_t))) ||
+        (rc = ensure(c->dn_tail[1].list, (cap + 1) * sizeof(uint32_t))))
         return rc;
     sdk::DnPrep p{};
     p.counter = static_cast<uint32_t*>(c->counter.p);
@@ -753,12 +851,11 @@ int dn_prep(sdk_ctx* c, uint64_t cap, bool first_pass) {
     for (int k = 0; k < 2; ++k) {
         p.ctl[k] = reinterpret_cast<uint32_t*>(static_cast<char*>(c->dn.p) + (size_t)k * sdk::kDnBytes);
         p.epoch[k] = ++c->dn_epoch;
+        p.list[k] = static_cast<uint32_t*>(c->dn_tail[k].list.p);
     }
     p.fault = c->dn_fault ? 1u : 0u;
     p.helpers = (uint32_t)c->dn_helpers;
-    p.list[0] = static_cast<uint32_t*>(c->dn_list.p);
-    p.list[1] = static_cast<uint32_t*>(c->dn3_list.p);
-    if (c->dn_resume_now) {
+    if (resume) {
         if ((rc = ensure(c->dn_save, sizeof(sdk::SplitSave))) || (rc = ensure(c->dn_save_idx, (size_t)cap * 4)) ||
             (rc = ensure(c->dn_seeds, (2 + 2 * (size_t)sdk::kSeedBoards) * 4)))
             return rc;
@@ -770,30 +867,34 @@ int dn_prep(sdk_ctx* c, uint64_t cap, bool first_pass) {
     return SDK_OK;
 }
 
-int launch_prop32_solve(sdk_ctx* c, const uint8_t* d_in, uint8_t* d_out, int8_t* d_status, size_t n, int order,
-                        int64_t budget, int64_t donate);
+int launch_prop32_solve(sdk_ctx* c, const SolveCall& s);
 
-int launch_solve(sdk_ctx* c, const uint8_t* d_in, const uint16_t* d_mask, uint8_t* d_out, int8_t* d_status,
-                 uint64_t* d_work, size_t n, int count_mode, uint64_t limit, unsigned long long* d_count,
-                 unsigned long long* d_counts = nullptr, uint64_t in_first = 0, uint64_t in_step = 1,
-                 int order = -1, int64_t budget = -1, int64_t donate = -1, const uint32_t* n_dev = nullptr) {
-    // donate: SDK_OPT_DONATE for this call (-1 = the context's); n_dev: the batch's length on the
-    // device (n bounds it; the prop32 fallback)
-    const int eff_order = order >= 0 ? order : c->order;
-    const uint64_t node_budget = budget >= 0 ? (uint64_t)budget : c->budget;
+// The solve launch described above kDnCapBoards.  Everything about the call is in `call`: of the
+// context this reads options and workspaces and writes only the outcome fields (dn_ran, prop32_ran,
+// dn_err_check).  The call's -1 fields are resolved once, here; the resolved call `s` is what the
+// prop32 pass, the phases and the fallback get.
+int launch_solve(sdk_ctx* c, const SolveCall& call) {
+    SolveCall s = call;
+    if (s.order < 0) s.order = c->order;
+    if (s.budget < 0) s.budget = (int64_t)c->budget;
+    if (s.donate < 0) s.donate = c->donate;
+    if (s.solver < 0) s.solver = c->solver;
+    const size_t n = s.n;
+    const uint32_t* n_dev = s.n_dev;
+    const uint64_t node_budget = (uint64_t)s.budget;
     if (!n_dev) c->prop32_ran = false;
     // the bit-sliced root propagation pass first (prop32_kernel.h): plain solves of whole batches
     // (no first-cell masks, work counters, strided inputs or first-solution scans), 16-byte
     // aligned, at least prop32_min boards; a budget of 1 node is left to solve4 (a board solved at
     // its root takes one); prop32 always runs locked-candidates passes, so with SDK_OPT_LOCKED 0
     // it only runs where no budget can tell the difference
-    if (!n_dev && c->prop32 && c->solver == SDK_SOLVER_QUAD && !count_mode && d_out && d_status && !d_work &&
-        !d_mask && in_first == 0 && in_step <= 1 && !c->first_found &&
+    if (!n_dev && c->prop32 && s.solver == SDK_SOLVER_QUAD && !s.count_mode && s.out && s.status && !s.work &&
+        !s.mask && s.in_first == 0 && s.in_step <= 1 && !s.found &&
         (node_budget == 0 || (node_budget >= 2 && c->locked)) &&
         (int64_t)n >= c->prop32_min && n <= kDnCapBoards &&
-        ((reinterpret_cast<uintptr_t>(d_in) | reinterpret_cast<uintptr_t>(d_out)) & 15u) == 0)
-        return launch_prop32_solve(c, d_in, d_out, d_status, n, order, budget, donate);
-    const int64_t dn = donate >= 0 ? donate : (int64_t)c->donate;
+        ((reinterpret_cast<uintptr_t>(s.in) | reinterpret_cast<uintptr_t>(s.out)) & 15u) == 0)
+        return launch_prop32_solve(c, s);
+    const int64_t dn = s.donate;
     // the default split budget doubles above 2^19 SEARCHED boards (sdk::kBudgetBigBoards; a prop32
     // fallback batch's count is on the device, so its split launch picks the budget there): with ~30
     // boards per slot a heavy board's extra nodes overlap the bulk, and fewer boards reach the
@@ -805,10 +906,10 @@ int launch_solve(sdk_ctx* c, const uint8_t* d_in, const uint16_t* d_mask, uint8_
                                       : (uint64_t)dn;
     // (only where the node budget leaves room for it: with a budget B <= 256 a board needing
     // more than B nodes must end as a budget hit, which the split phase at 256 would solve)
-    c->split_big = split_auto && n_dev && (node_budget == 0 || node_budget > 2 * kDnSplitDefault)
-                       ? 2 * kDnSplitDefault : 0;
-    const bool two_phase = n > 0 && !count_mode && dn && c->solver == SDK_SOLVER_QUAD &&
-                           (eff_order == SDK_ORDER_LEX || eff_order == SDK_ORDER_MRV_UNIQUE) && d_out && d_status &&
+    const uint64_t split_big = split_auto && n_dev && (node_budget == 0 || node_budget > 2 * kDnSplitDefault)
+                                   ? 2 * kDnSplitDefault : 0;
+    const bool two_phase = n > 0 && !s.count_mode && dn && s.solver == SDK_SOLVER_QUAD &&
+                           (s.order == SDK_ORDER_LEX || s.order == SDK_ORDER_MRV_UNIQUE) && s.out && s.status &&
                            (node_budget == 0 || node_budget > split) &&
                            // a prop32 fallback batch (n_dev) holds only boards propagation left open:
                            // phased at any size (1M hard boards: 6.8 ms phased vs 8.3 in one launch,
@@ -820,45 +921,43 @@ int launch_solve(sdk_ctx* c, const uint8_t* d_in, const uint16_t* d_mask, uint8_
     // exhaustive (MRV) donation launch: LEX items there cost more nodes than a restart in MRV
     // order (heavy 1000: 80k vs 61k nodes, 1.56 vs 1.30 ms), and LEX acceptance in a LEX
     // donation launch would need the closed prefixes MRV stacks do not have
-    c->dn_resume_now = two_phase && c->dn_resume && c->dn_exhaustive && eff_order == SDK_ORDER_MRV_UNIQUE;
-    if (!two_phase)
-        return launch_solve_once(c, d_in, d_mask, d_out, d_status, d_work, n, count_mode, limit, d_count, d_counts,
-                                 in_first, in_step, order, budget, 0, n_dev);
+    const bool resume = two_phase && c->dn_resume && c->dn_exhaustive && s.order == SDK_ORDER_MRV_UNIQUE;
+    if (!two_phase) return launch_solve_once(c, s);
     if (n_dev && n > kDnCapBoards) return fail(SDK_EINVAL, "a device-counted batch is solved in one pass");
     // SDK_OPT_TIMING: the phases of one solve are one timed span
-    hipEvent_t stop;
-    int rc = timer_begin(c, &stop);
+    TimedSpan span(c);
+    int rc = span.begin();
     if (rc) return rc;
-    c->timer_hold = true;
-    const uint64_t step = in_step ? in_step : 1;
+    const SolvePhase split_phase{SolvePhase::kSplit, nullptr, split_big, resume};
+    const uint64_t step = s.in_step ? s.in_step : 1;
     for (uint64_t b0 = 0; b0 < n && !rc; b0 += kDnCapBoards) {
-        const uint64_t m = std::min<uint64_t>(n - b0, kDnCapBoards);
-        uint8_t* out = d_out + b0 * 81;
-        int8_t* st = d_status + b0;
-        uint64_t* work = d_work ? d_work + b0 : nullptr;
-        const uint16_t* mask = d_mask ? d_mask + b0 : nullptr;
-        const uint64_t first = in_first + b0 * step;
-        (void)((rc = dn_prep(c, m, b0 == 0)) ||
-               (rc = launch_solve_once(c, d_in, mask, out, st, work, m, 0, 0, nullptr, nullptr, first, step, order,
-                                       (int64_t)split, 1, n_dev)) ||
-               (rc = dn_collect(c, st, m, n_dev, (int8_t)-2, c->dn_list, 0, d_in, mask, first, step, c->dn_in,
-                                c->dn_mask, c->dn_resume_now)) ||
-               (rc = dn_resolve(c, m, c->dn_list, 0, mask != nullptr, out, st, work,
-                                c->dn_exhaustive ? SDK_ORDER_MRV_UNIQUE : SDK_ORDER_LEX, (int64_t)node_budget, c->dn_in,
-                                c->dn_mask, c->dn_out, c->dn_st, c->dn_work,
-                                c->dn_resume_now ? static_cast<uint32_t*>(c->dn_seeds.p) + 1 : nullptr)));
+        SolveCall pass = s;          // this pass's boards: kDnCapBoards of the call's from b0
+        pass.n = std::min<uint64_t>(n - b0, kDnCapBoards);
+        pass.out = s.out + b0 * 81;
+        pass.status = s.status + b0;
+        pass.work = s.work ? s.work + b0 : nullptr;
+        pass.mask = s.mask ? s.mask + b0 : nullptr;
+        pass.in_first = s.in_first + b0 * step;
+        pass.in_step = step;
+        SolveCall split_call = pass;  // ... every one of them first with the split budget
+        split_call.budget = (int64_t)split;
+        (void)((rc = dn_prep(c, pass.n, b0 == 0, resume)) ||
+               (rc = launch_solve_once(c, split_call, split_phase)) ||
+               (rc = dn_collect(c, pass, (int8_t)-2, 0, resume)) ||
+               (rc = dn_resolve(c, pass, 0, c->dn_exhaustive ? SDK_ORDER_MRV_UNIQUE : SDK_ORDER_LEX,
+                                resume ? static_cast<uint32_t*>(c->dn_seeds.p) + 1 : nullptr)));
     }
-    c->timer_hold = false;
-    if (rc) return rc;
-    return timer_end(c, stop);
+    return span.end(rc);
 }
 
 // The prop32 pass (prop32_kernel.h) over the batch, then the boards it leaves undecided -- listed
 // with their inputs on the device -- solved by the usual path (solve4, phased with donation when
 // that applies) with the list's length read on the device, and their answers scattered back.
 // Every launch is enqueued at once; an empty list costs the fallback's launches a few microseconds.
-int launch_prop32_solve(sdk_ctx* c, const uint8_t* d_in, uint8_t* d_out, int8_t* d_status, size_t n, int order,
-                        int64_t budget, int64_t donate) {
+// `s` is the resolved call launch_solve's gate let through: plain (no masks, work counters, stride or
+// found word), so the fallback is the same call over the list's boards.
+int launch_prop32_solve(sdk_ctx* c, const SolveCall& s) {
+    const size_t n = s.n;
     int rc;
     constexpr size_t kCtlBytes = (size_t)sdk::kP32Heads * sdk::kP32HeadStride * 4;
     if ((rc = ensure(c->p32_ctl, kCtlBytes)) || (rc = ensure(c->p32_list, (n + 1) * 4)) ||
@@ -870,9 +969,9 @@ int launch_prop32_solve(sdk_ctx* c, const uint8_t* d_in, uint8_t* d_out, int8_t*
     hipEvent_t stop;
     if ((rc = timer_begin(c, &stop))) return rc;
     sdk::Prop32Args a{};
-    a.in = d_in;
-    a.out = d_out;
-    a.status = d_status;
+    a.in = s.in;
+    a.out = s.out;
+    a.status = s.status;
     a.n = n;
     a.heads = static_cast<uint32_t*>(c->p32_ctl.p);
     a.list = static_cast<uint32_t*>(c->p32_list.p);
@@ -882,12 +981,10 @@ int launch_prop32_solve(sdk_ctx* c, const uint8_t* d_in, uint8_t* d_out, int8_t*
     a.max_steps = 96;
     // the search continues from the propagated grids when no node budget applies (a budget counts
     // nodes from the input, so the statuses of budget hits would differ)
-    const uint64_t node_budget = budget >= 0 ? (uint64_t)budget : c->budget;
-    a.handover = (c->prop32_handover && node_budget == 0) ? 1 : 0;
+    a.handover = (c->prop32_handover && s.budget == 0) ? 1 : 0;
     a.tail_live = a.handover ? (uint32_t)c->prop32_tail_live : 0u;
     a.tail_step = (uint32_t)c->prop32_tail_step;
-    const uint64_t groups = (n + 63) / 64;
-    const unsigned grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(groups, (uint64_t)c->cus * 20));
+    const unsigned grid = grid_for(c, n, 64, 20);   // a group of 64 boards per dequeue
     uint64_t* stamps = nullptr;
     if (c->clock_probe) {      // the diagnostic twin (sdk_debug_clock_arm)
         if ((rc = ensure(c->p32_stamps, (size_t)grid * 32))) return rc;
@@ -895,24 +992,23 @@ int launch_prop32_solve(sdk_ctx* c, const uint8_t* d_in, uint8_t* d_out, int8_t*
         c->p32_stamp_wgs = grid;
     }
     HIPCALL(sdk::launch_prop32(a, grid, c->stream, stamps));
-    if ((rc = timer_end(c, stop)) || (rc = timer_begin(c, &stop))) return rc;
-    const bool held = c->timer_hold;   // a minimise call holds the timer over all its rounds
-    c->timer_hold = true;
+    TimedSpan span(c);
+    if ((rc = timer_end(c, stop)) || (rc = span.begin())) return rc;
     c->prop32_ran = true;
-    const uint32_t* lst = static_cast<const uint32_t*>(c->p32_list.p);
-    rc = launch_solve(c, static_cast<uint8_t*>(c->p32_in.p), nullptr, static_cast<uint8_t*>(c->p32_out.p),
-                      static_cast<int8_t*>(c->p32_st.p), nullptr, n, 0, 0, nullptr, nullptr, 0, 1, order, budget,
-                      donate, lst);
+    SolveCall rest = s;     // the same order, budget, donate and solver over the list's boards
+    rest.in = static_cast<uint8_t*>(c->p32_in.p);
+    rest.out = static_cast<uint8_t*>(c->p32_out.p);
+    rest.status = static_cast<int8_t*>(c->p32_st.p);
+    rest.n_dev = static_cast<const uint32_t*>(c->p32_list.p);
+    rest.in_step = 1;
+    rc = launch_solve(c, rest);
     if (!rc) {
         // one thread per 4 bytes of the list's boards (its length is on the device: sized for all n)
-        const unsigned g = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n * 81 + 1023) / 1024, (uint64_t)c->cus * 8));
-        if (sdk::launch_p32_scatter(lst, static_cast<uint8_t*>(c->p32_out.p), static_cast<int8_t*>(c->p32_st.p), d_in,
-                                    d_out, d_status, g, c->stream) != hipSuccess)
+        if (sdk::launch_p32_scatter(rest.n_dev, rest.out, rest.status, s.in, s.out, s.status,
+                                    grid_for(c, n * 81, 1024, 8), c->stream) != hipSuccess)
             rc = fail(SDK_EHIP, "prop32 scatter launch failed");
     }
-    c->timer_hold = held;
-    if (rc) return rc;
-    return timer_end(c, stop);
+    return span.end(rc);
 }
 
 // Classify launch (sdk_classify_batch): the solve path with ORDER_CLASSIFY -- the prop32 pass under
@@ -920,19 +1016,21 @@ int launch_prop32_solve(sdk_ctx* c, const uint8_t* d_in, uint8_t* d_out, int8_t*
 // then ONE plain QUAD launch over the boards it left (no phases, no donation: launch_solve's
 // two_phase is false for this order), whatever SDK_OPT_SOLVER and SDK_OPT_ORDER say.  Batches above
 // kDnCapBoards (the pass's cap) go in slices of that many, so every slice gets the pass.
-// Nothing of the call outlives it: the solver option is put back, and dn_ran, dn_resume_now and
-// split_big are left as a one-launch solve leaves them.
+// budget: search nodes per board, -1 = the context's.
 int launch_classify(sdk_ctx* c, const uint8_t* d_in, uint8_t* d_out, int8_t* d_status, size_t n, int64_t budget) {
-    const int solver = c->solver;
-    c->solver = SDK_SOLVER_QUAD;
+    SolveCall s;
+    s.order = sdk::ORDER_CLASSIFY;
+    s.solver = SDK_SOLVER_QUAD;
+    s.budget = budget;
+    s.donate = 0;
     int rc = SDK_OK;
     for (uint64_t b0 = 0; b0 < n && !rc; b0 += kDnCapBoards) {
-        const uint64_t m = std::min<uint64_t>(n - b0, kDnCapBoards);
-        rc = launch_solve(c, d_in + b0 * 81, nullptr, d_out + b0 * 81, d_status + b0, nullptr, m, 0, 0, nullptr,
-                          nullptr, 0, 1, sdk::ORDER_CLASSIFY, budget, 0);
+        s.in = d_in + b0 * 81;
+        s.out = d_out + b0 * 81;
+        s.status = d_status + b0;
+        s.n = std::min<uint64_t>(n - b0, kDnCapBoards);
+        rc = launch_solve(c, s);
     }
-    c->solver = solver;
-    c->split_big = 0;
     return rc;
 }
 
@@ -949,10 +1047,8 @@ int launch_minimize(sdk_ctx* c, const uint8_t* d_in, const uint8_t* d_order, uin
     int rc;
     if ((rc = ensure(c->mz_cand, cap * 81)) || (rc = ensure(c->mz_out, cap * 81)) || (rc = ensure(c->mz_st, cap)))
         return rc;
-    hipEvent_t stop;
-    if ((rc = timer_begin(c, &stop))) return rc;
-    const bool held = c->timer_hold;
-    c->timer_hold = true;
+    TimedSpan span(c);
+    if ((rc = span.begin())) return rc;
     uint8_t* cand = static_cast<uint8_t*>(c->mz_cand.p);
     uint8_t* scratch = static_cast<uint8_t*>(c->mz_out.p);
     int8_t* cst = static_cast<int8_t*>(c->mz_st.p);
@@ -964,7 +1060,7 @@ int launch_minimize(sdk_ctx* c, const uint8_t* d_in, const uint8_t* d_order, uin
         a.status = d_status + b0;
         a.cst = cst;
         a.n = m;
-        const unsigned grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((m * 81 + 1023) / 1024, (uint64_t)c->cus * 8));
+        const unsigned grid = grid_for(c, m * 81, 1024, 8);
         // the inputs' verdicts (the completions go to scratch: `out` starts as the inputs)
         rc = launch_classify(c, d_in + b0 * 81, scratch, d_status + b0, m, 0);
         for (uint32_t q = 0; q <= 81 && !rc; ++q) {
@@ -976,9 +1072,7 @@ int launch_minimize(sdk_ctx* c, const uint8_t* d_in, const uint8_t* d_order, uin
             if (!rc && q < 81) rc = launch_classify(c, cand, scratch, cst, m, 0);
         }
     }
-    c->timer_hold = held;
-    if (rc) return rc;
-    return timer_end(c, stop);
+    return span.end(rc);
 }
 
 // Deterministic breadth-first frontier of one board, left in c->fr_a.
@@ -1023,13 +1117,11 @@ int run_frontier_levels(sdk_ctx* c, uint64_t m0, bool use_mask, int mode, uint64
     h.m = m0;
     HIPCALL(hipMemcpyAsync(ctl, &h, sizeof h, hipMemcpyHostToDevice, c->stream));
     void* buf[2] = {c->fr_a.p, c->fr_b.p};
-    const unsigned eg = (unsigned)std::max<uint64_t>(
-        1, std::min<uint64_t>((m_exp + sdk::kChunk - 1) / sdk::kChunk, (uint64_t)c->cus * c->waves_per_cu));
+    const unsigned eg = grid_for(c, m_exp, sdk::kChunk, c->waves_per_cu);
     const bool quad = c->solver == SDK_SOLVER_QUAD;
-    const unsigned eg4 = (unsigned)std::max<uint64_t>(
-        1, std::min<uint64_t>((m_exp + 3) / 4, (uint64_t)c->cus * c->waves_per_cu2));
-    const unsigned sg = (unsigned)std::min<uint64_t>(tiles, (uint64_t)c->cus * 4);
-    const unsigned gg = (unsigned)std::min<uint64_t>(m_exp, (uint64_t)c->cus * 32);
+    const unsigned eg4 = grid_for(c, m_exp, 4, c->waves_per_cu2);
+    const unsigned sg = grid_for(c, m_exp, sdk::kScanTile, 4);   // (m_exp >= 1: no grid is empty)
+    const unsigned gg = grid_for(c, m_exp, 1, 32);
     hipEvent_t stop;
     if ((rc = timer_begin(c, &stop))) return rc;
     constexpr int kLevelsPerSync = 4;
@@ -1104,9 +1196,8 @@ int refine_frontier(sdk_ctx* c, uint64_t first, uint64_t step, uint64_t end, uin
     // fr_b takes the share and becomes fr_a: size it for the whole refinement now
     if ((rc = ensure(c->fr_b, frontier_capacity(std::max<uint64_t>(n, 1), target) * 81))) return rc;
     if (n) {
-        const unsigned g = (unsigned)std::min<uint64_t>((n + 3) / 4, (uint64_t)c->cus * 16);
-        sdk::gather_boards_kernel<<<g, 256, 0, c->stream>>>(static_cast<const uint8_t*>(c->fr_a.p), first, step, n,
-                                                           static_cast<uint8_t*>(c->fr_b.p));
+        sdk::gather_boards_kernel<<<grid_for(c, n, 4, 16), 256, 0, c->stream>>>(
+            static_cast<const uint8_t*>(c->fr_a.p), first, step, n, static_cast<uint8_t*>(c->fr_b.p));
         HIPCALL(hipGetLastError());
     }
     std::swap(c->fr_a, c->fr_b);
@@ -1169,29 +1260,22 @@ int expand_boards(sdk_ctx* c, const uint8_t* h_in, const uint16_t* h_masks, uint
     if (n > kFrontierCap) return fail(SDK_EINVAL, "at most %llu seed boards", (unsigned long long)kFrontierCap);
     int rc;
     if ((rc = ensure(c->fr_a, frontier_capacity(n, target) * 81)) || (rc = ensure(c->fr_mask, n * 2))) return rc;
-    // through the pinned staging area (see HostBuf); run_frontier_levels synchronizes before returning
-    char* st = static_cast<char*>(stage_host(c->stage, n * 83));
-    if (st) {
-        std::memcpy(st, h_in, n * 81);
-        if (h_masks) std::memcpy(st + n * 81, h_masks, n * 2);
-    }
-    DrainOnError drain{c->stream, true};    // also covers the pageable path's output copy
-    HIPCALL(hipMemcpyAsync(c->fr_a.p, st ? st : (const char*)h_in, n * 81, hipMemcpyHostToDevice, c->stream));
-    if (h_masks)
-        HIPCALL(hipMemcpyAsync(c->fr_mask.p, st ? st + n * 81 : (const char*)h_masks, n * 2, hipMemcpyHostToDevice,
-                               c->stream));
-    if ((rc = run_frontier_levels(c, n, h_masks != nullptr, SDK_FRONTIER_FIRST, target, true))) return rc;
+    // (the seed boards sit at offset 0, where every type is aligned; the masks after them, at 81 n,
+    // are copied as bytes)
+    Staging seeds(c, {{n * 81, h_in, c->fr_a.p}, {n * 2, h_masks, c->fr_mask.p}});
+    // run_frontier_levels synchronizes before returning, so the area is free for the frontier, whose
+    // size is known only then: a staging of its own (nothing comes back through the seeds' one,
+    // whose fetch() only ends it)
+    if ((rc = seeds.send()) || (rc = run_frontier_levels(c, n, h_masks != nullptr, SDK_FRONTIER_FIRST, target, true)) ||
+        (rc = seeds.fetch()))
+        return rc;
     if (c->fr_size > cap)
         return fail(SDK_EINVAL, "frontier of %llu boards exceeds cap %llu (pass cap >= 9 * max(n, target))",
                     (unsigned long long)c->fr_size, (unsigned long long)cap);
     if (c->fr_size) {
-        char* so = static_cast<char*>(stage_host(c->stage, c->fr_size * 81));
-        HIPCALL(hipMemcpyAsync(so ? so : (char*)h_out, c->fr_a.p, c->fr_size * 81, hipMemcpyDeviceToHost, c->stream));
-        HIPCALL(hipStreamSynchronize(c->stream));
-        if (so) std::memcpy(h_out, so, c->fr_size * 81);
+        Staging frontier(c, {{c->fr_size * 81, nullptr, nullptr, c->fr_a.p, h_out}});
+        if ((rc = frontier.fetch())) return rc;
     }
-    HIPCALL(hipStreamSynchronize(c->stream));
-    drain.armed = false;
     *out_n = c->fr_size;
     return SDK_OK;
 }
@@ -1209,9 +1293,13 @@ int frontier_count(sdk_ctx* c, uint64_t first, uint64_t step, uint64_t end, uint
     unsigned long long* d_count = static_cast<unsigned long long*>(c->counter.p) + 3;
     HIPCALL(hipMemsetAsync(d_count, 0, 8, c->stream));
     if (n) {
-        rc = launch_solve(c, static_cast<uint8_t*>(c->fr_a.p), nullptr, nullptr, static_cast<int8_t*>(c->fr_status.p),
-                          nullptr, n, 1, limit, d_count, nullptr, first, step);
-        if (rc) return rc;
+        SolveCall s{static_cast<uint8_t*>(c->fr_a.p), nullptr, nullptr, static_cast<int8_t*>(c->fr_status.p), nullptr, n};
+        s.in_first = first;
+        s.in_step = step;
+        s.count_mode = 1;
+        s.limit = limit;
+        s.count = d_count;
+        if ((rc = launch_solve(c, s))) return rc;
     }
     sdk::count_result_kernel<<<1, 256, 0, c->stream>>>(static_cast<int8_t*>(c->fr_status.p), n, d_count, d_result);
     HIPCALL(hipGetLastError());
@@ -1233,11 +1321,12 @@ int frontier_first(sdk_ctx* c, uint64_t lo, uint64_t hi, long long* d_found, uin
         // (no subtree donation: a heavy board is split by the caller, shard.sharded_solve)
         sdk::first_init_kernel<<<1, 1, 0, c->stream>>>(d_found);
         HIPCALL(hipGetLastError());
-        c->first_found = d_found;
-        rc = launch_solve(c, static_cast<uint8_t*>(c->fr_a.p), nullptr, static_cast<uint8_t*>(c->out.p),
-                          static_cast<int8_t*>(c->status.p), nullptr, n, 0, 0, nullptr, nullptr, lo, 1, -1, -1, 0);
-        c->first_found = nullptr;
-        if (rc) return rc;
+        SolveCall s{static_cast<uint8_t*>(c->fr_a.p), nullptr, static_cast<uint8_t*>(c->out.p),
+                    static_cast<int8_t*>(c->status.p), nullptr, n};
+        s.in_first = lo;
+        s.donate = 0;
+        s.found = d_found;
+        if ((rc = launch_solve(c, s))) return rc;
     }
     sdk::first_hit_kernel<<<1, 256, 0, c->stream>>>(static_cast<int8_t*>(c->status.p),
                                                     static_cast<uint8_t*>(c->out.p), n, lo, d_found, d_best);
@@ -1510,7 +1599,7 @@ extern "C" int sdk_debug_clock_read(sdk_ctx* c, double* out4, int64_t* workgroup
 // (not deterministic: workgroups reserve list slots with an atomic add) -- index[i] the board's
 // index in the batch, grids[81 i ..] what the search was given for it (p32_in: the propagated grid
 // under handover, else the input; the fallback only reads that buffer -- launch_solve takes it as
-// its const input and dn_collect copies from it into dn_in).
+// its const input and dn_collect copies from it into dn_tail[0].in).
 extern "C" int sdk_debug_p32_list(sdk_ctx* c, uint32_t* index, uint8_t* grids, int64_t cap, int64_t* count) {
     if (!c || !count || cap < 0 || (cap > 0 && (!index || !grids))) return fail(SDK_EINVAL, "NULL argument");
     std::lock_guard<std::mutex> lk(c->mu);
@@ -1733,9 +1822,9 @@ int sdk_solve_batch_dev(sdk_ctx* c, const void* d_in, const void* d_mask, void* 
     if (!c || (n && (!d_in || !d_out || !d_status))) return fail(SDK_EINVAL, "NULL argument");
     std::lock_guard<std::mutex> lk(c->mu);
     HIPCALL(hipSetDevice(c->device));
-    return launch_solve(c, static_cast<const uint8_t*>(d_in), static_cast<const uint16_t*>(d_mask),
-                        static_cast<uint8_t*>(d_out), static_cast<int8_t*>(d_status), static_cast<uint64_t*>(d_work),
-                        n, 0, 0, nullptr);
+    return launch_solve(c, SolveCall{static_cast<const uint8_t*>(d_in), static_cast<const uint16_t*>(d_mask),
+                                     static_cast<uint8_t*>(d_out), static_cast<int8_t*>(d_status),
+                                     static_cast<uint64_t*>(d_work), n});
 }
 
 int sdk_check_batch(sdk_ctx* c, const uint8_t* boards, uint8_t* verdict, size_t n) {
@@ -1765,8 +1854,7 @@ int sdk_check_batch_i64(sdk_ctx* c, const int64_t* boards, uint8_t* verdict, siz
     HIPCALL(hipMemcpyAsync(c->in.p, boards, n * 81 * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
     hipEvent_t stop;
     if ((rc = timer_begin(c, &stop))) return rc;
-    const unsigned grid = (unsigned)std::min<uint64_t>((n + 255) / 256, (uint64_t)c->cus * 8);
-    sdk::check_kernel_i64<<<grid, 256, 0, c->stream>>>(static_cast<const int64_t*>(c->in.p),
+    sdk::check_kernel_i64<<<grid_for(c, n, 256, 8), 256, 0, c->stream>>>(static_cast<const int64_t*>(c->in.p),
                                                       static_cast<uint8_t*>(c->verdict.p), (uint64_t)n);
     HIPCALL(hipGetLastError());
     if ((rc = timer_end(c, stop))) return rc;
@@ -1788,98 +1876,63 @@ int sdk_solve_batch_budget(sdk_ctx* c, const uint8_t* in, const uint16_t* first_
 int sdk_solve_batch_ex(sdk_ctx* c, const uint8_t* in, const uint16_t* first_cell_mask, uint8_t* out, int8_t* status,
                        uint64_t* work, size_t n, uint64_t node_budget, int64_t donate) {
     if (!c || (n && (!in || !out || !status))) return fail(SDK_EINVAL, "NULL argument");
-    if (node_budget != SDK_BUDGET_CONTEXT && node_budget > (uint64_t)INT64_MAX)
-        return fail(SDK_EINVAL, "node budget out of range");
+    int rc;
+    if ((rc = check_budget_arg(node_budget))) return rc;
     if (donate < SDK_DONATE_CONTEXT || donate > (1 << 30))
         return fail(SDK_EINVAL, "donate must be SDK_DONATE_CONTEXT, 0, 1 or a split budget >= 2");
     if (n == 0) return SDK_OK;
     std::lock_guard<std::mutex> lk(c->mu);
     HIPCALL(hipSetDevice(c->device));
-    int rc;
     if ((rc = ensure(c->in, n * 81)) || (rc = ensure(c->out, n * 81)) || (rc = ensure(c->status, n))) return rc;
     if (first_cell_mask && (rc = ensure(c->mask, n * 2))) return rc;
     if (work && (rc = ensure(c->work, n * 8))) return rc;
-    // staging layout: work (n x 8), masks (n x 2), in / out boards (n x 81), status (n)
-    char* st = static_cast<char*>(stage_host(c->stage, n * (8 + 2 + 81 + 1)));
-    uint64_t* s_work = reinterpret_cast<uint64_t*>(st);
-    uint16_t* s_mask = st ? reinterpret_cast<uint16_t*>(st + n * 8) : nullptr;
-    uint8_t* s_io = st ? reinterpret_cast<uint8_t*>(st + n * 10) : nullptr;
-    int8_t* s_st = st ? reinterpret_cast<int8_t*>(st + n * 91) : nullptr;
-    if (st) {
-        std::memcpy(s_io, in, n * 81);
-        if (first_cell_mask) std::memcpy(s_mask, first_cell_mask, n * 2);
-    }
-    DrainOnError drain{c->stream, st != nullptr};
-    HIPCALL(hipMemcpyAsync(c->in.p, st ? s_io : in, n * 81, hipMemcpyHostToDevice, c->stream));
-    if (first_cell_mask)
-        HIPCALL(hipMemcpyAsync(c->mask.p, st ? s_mask : first_cell_mask, n * 2, hipMemcpyHostToDevice, c->stream));
-    rc = launch_solve(c, static_cast<uint8_t*>(c->in.p), first_cell_mask ? static_cast<uint16_t*>(c->mask.p) : nullptr,
-                      static_cast<uint8_t*>(c->out.p), static_cast<int8_t*>(c->status.p),
-                      work ? static_cast<uint64_t*>(c->work.p) : nullptr, n, 0, 0, nullptr, nullptr, 0, 1, -1,
-                      node_budget == SDK_BUDGET_CONTEXT ? -1 : (int64_t)node_budget, donate);
-    if (rc) return rc;
-    HIPCALL(hipMemcpyAsync(st ? s_io : out, c->out.p, n * 81, hipMemcpyDeviceToHost, c->stream));
-    HIPCALL(hipMemcpyAsync(st ? s_st : status, c->status.p, n, hipMemcpyDeviceToHost, c->stream));
-    if (work) HIPCALL(hipMemcpyAsync(st ? s_work : work, c->work.p, n * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCALL(hipStreamSynchronize(c->stream));
-    drain.armed = false;
-    if (st) {
-        std::memcpy(out, s_io, n * 81);
-        std::memcpy(status, s_st, n);
-        if (work) std::memcpy(work, s_work, n * 8);
-    }
+    SolveCall s{static_cast<uint8_t*>(c->in.p), first_cell_mask ? static_cast<uint16_t*>(c->mask.p) : nullptr,
+                static_cast<uint8_t*>(c->out.p), static_cast<int8_t*>(c->status.p),
+                work ? static_cast<uint64_t*>(c->work.p) : nullptr, n};
+    s.budget = budget_arg(node_budget);
+    s.donate = donate;
+    Staging io(c, {{n * 8, nullptr, nullptr, s.work, work},      // (a slot each, present or not)
+                   {n * 2, first_cell_mask, c->mask.p},
+                   {n * 81, in, c->in.p, s.out, out},
+                   {n, nullptr, nullptr, s.status, status}});
+    if ((rc = io.send()) || (rc = launch_solve(c, s)) || (rc = io.fetch())) return rc;
     return dn_check_error(c);
 }
 
 int sdk_classify_batch_dev(sdk_ctx* c, const void* d_in, void* d_out, void* d_status, size_t n, uint64_t node_budget) {
     if (!c || (n && (!d_in || !d_out || !d_status))) return fail(SDK_EINVAL, "NULL argument");
-    if (node_budget != SDK_BUDGET_CONTEXT && node_budget > (uint64_t)INT64_MAX)
-        return fail(SDK_EINVAL, "node budget out of range");
+    int rc;
+    if ((rc = check_budget_arg(node_budget))) return rc;
     if (n == 0) return SDK_OK;
-    if (n > 0x7FFFFFFFull) return fail(SDK_EINVAL, "at most 2^31-1 boards per call");
+    if ((rc = check_board_count(n))) return rc;
     std::lock_guard<std::mutex> lk(c->mu);
     HIPCALL(hipSetDevice(c->device));
     return launch_classify(c, static_cast<const uint8_t*>(d_in), static_cast<uint8_t*>(d_out),
-                           static_cast<int8_t*>(d_status), n,
-                           node_budget == SDK_BUDGET_CONTEXT ? -1 : (int64_t)node_budget);
+                           static_cast<int8_t*>(d_status), n, budget_arg(node_budget));
 }
 
 int sdk_classify_batch(sdk_ctx* c, const uint8_t* in, uint8_t* out, int8_t* status, size_t n, uint64_t node_budget) {
     if (!c || (n && (!in || !out || !status))) return fail(SDK_EINVAL, "NULL argument");
-    if (node_budget != SDK_BUDGET_CONTEXT && node_budget > (uint64_t)INT64_MAX)
-        return fail(SDK_EINVAL, "node budget out of range");
+    int rc;
+    if ((rc = check_budget_arg(node_budget))) return rc;
     if (n == 0) return SDK_OK;
-    if (n > 0x7FFFFFFFull) return fail(SDK_EINVAL, "at most 2^31-1 boards per call");
+    if ((rc = check_board_count(n))) return rc;
     std::lock_guard<std::mutex> lk(c->mu);
     HIPCALL(hipSetDevice(c->device));
-    int rc;
     if ((rc = ensure(c->in, n * 81)) || (rc = ensure(c->out, n * 81)) || (rc = ensure(c->status, n))) return rc;
-    // staging layout: in / out boards (n x 81), status (n)
-    char* st = static_cast<char*>(stage_host(c->stage, n * 82));
-    uint8_t* s_io = reinterpret_cast<uint8_t*>(st);
-    int8_t* s_st = st ? reinterpret_cast<int8_t*>(st + n * 81) : nullptr;
-    if (st) std::memcpy(s_io, in, n * 81);
-    DrainOnError drain{c->stream, st != nullptr};
-    HIPCALL(hipMemcpyAsync(c->in.p, st ? s_io : in, n * 81, hipMemcpyHostToDevice, c->stream));
-    if ((rc = launch_classify(c, static_cast<uint8_t*>(c->in.p), static_cast<uint8_t*>(c->out.p),
-                              static_cast<int8_t*>(c->status.p), n,
-                              node_budget == SDK_BUDGET_CONTEXT ? -1 : (int64_t)node_budget)))
-        return rc;
-    HIPCALL(hipMemcpyAsync(st ? s_io : out, c->out.p, n * 81, hipMemcpyDeviceToHost, c->stream));
-    HIPCALL(hipMemcpyAsync(st ? s_st : status, c->status.p, n, hipMemcpyDeviceToHost, c->stream));
-    HIPCALL(hipStreamSynchronize(c->stream));
-    drain.armed = false;
-    if (st) {
-        std::memcpy(out, s_io, n * 81);
-        std::memcpy(status, s_st, n);
-    }
-    return SDK_OK;
+    uint8_t* d_in = static_cast<uint8_t*>(c->in.p);
+    uint8_t* d_out = static_cast<uint8_t*>(c->out.p);
+    int8_t* d_status = static_cast<int8_t*>(c->status.p);
+    Staging io(c, {{n * 81, in, d_in, d_out, out}, {n, nullptr, nullptr, d_status, status}});
+    if ((rc = io.send()) || (rc = launch_classify(c, d_in, d_out, d_status, n, budget_arg(node_budget)))) return rc;
+    return io.fetch();
 }
 
 int sdk_minimize_batch_dev(sdk_ctx* c, const void* d_in, const void* d_order, void* d_out, void* d_status, size_t n) {
     if (!c || (n && (!d_in || !d_order || !d_out || !d_status))) return fail(SDK_EINVAL, "NULL argument");
     if (n == 0) return SDK_OK;
-    if (n > 0x7FFFFFFFull) return fail(SDK_EINVAL, "at most 2^31-1 boards per call");
+    int rc;
+    if ((rc = check_board_count(n))) return rc;
     std::lock_guard<std::mutex> lk(c->mu);
     HIPCALL(hipSetDevice(c->device));
     return launch_minimize(c, static_cast<const uint8_t*>(d_in), static_cast<const uint8_t*>(d_order),
@@ -1889,7 +1942,8 @@ int sdk_minimize_batch_dev(sdk_ctx* c, const void* d_in, const void* d_order, vo
 int sdk_minimize_batch(sdk_ctx* c, const uint8_t* in, const uint8_t* order, uint8_t* out, int8_t* status, size_t n) {
     if (!c || (n && (!in || !order || !out || !status))) return fail(SDK_EINVAL, "NULL argument");
     if (n == 0) return SDK_OK;
-    if (n > 0x7FFFFFFFull) return fail(SDK_EINVAL, "at most 2^31-1 boards per call");
+    int rc;
+    if ((rc = check_board_count(n))) return rc;
     // every order row is a permutation of 0..80
     for (size_t i = 0; i < n; ++i) {
         bool seen[81] = {};
@@ -1902,34 +1956,16 @@ int sdk_minimize_batch(sdk_ctx* c, const uint8_t* in, const uint8_t* order, uint
     }
     std::lock_guard<std::mutex> lk(c->mu);
     HIPCALL(hipSetDevice(c->device));
-    int rc;
     if ((rc = ensure(c->in, n * 81)) || (rc = ensure(c->mz_order, n * 81)) || (rc = ensure(c->out, n * 81)) ||
         (rc = ensure(c->status, n)))
         return rc;
-    // staging layout: order rows (n x 81), in / out boards (n x 81), status (n)
-    char* st = static_cast<char*>(stage_host(c->stage, n * 163));
-    uint8_t* s_ord = reinterpret_cast<uint8_t*>(st);
-    uint8_t* s_io = st ? reinterpret_cast<uint8_t*>(st + n * 81) : nullptr;
-    int8_t* s_st = st ? reinterpret_cast<int8_t*>(st + n * 162) : nullptr;
-    if (st) {
-        std::memcpy(s_ord, order, n * 81);
-        std::memcpy(s_io, in, n * 81);
-    }
-    DrainOnError drain{c->stream, st != nullptr};
-    HIPCALL(hipMemcpyAsync(c->in.p, st ? s_io : in, n * 81, hipMemcpyHostToDevice, c->stream));
-    HIPCALL(hipMemcpyAsync(c->mz_order.p, st ? s_ord : order, n * 81, hipMemcpyHostToDevice, c->stream));
-    if ((rc = launch_minimize(c, static_cast<uint8_t*>(c->in.p), static_cast<uint8_t*>(c->mz_order.p),
-                              static_cast<uint8_t*>(c->out.p), static_cast<int8_t*>(c->status.p), n)))
-        return rc;
-    HIPCALL(hipMemcpyAsync(st ? s_io : out, c->out.p, n * 81, hipMemcpyDeviceToHost, c->stream));
-    HIPCALL(hipMemcpyAsync(st ? s_st : status, c->status.p, n, hipMemcpyDeviceToHost, c->stream));
-    HIPCALL(hipStreamSynchronize(c->stream));
-    drain.armed = false;
-    if (st) {
-        std::memcpy(out, s_io, n * 81);
-        std::memcpy(status, s_st, n);
-    }
-    return SDK_OK;
+    uint8_t* d_in = static_cast<uint8_t*>(c->in.p);
+    uint8_t* d_order = static_cast<uint8_t*>(c->mz_order.p);
+    uint8_t* d_out = static_cast<uint8_t*>(c->out.p);
+    int8_t* d_status = static_cast<int8_t*>(c->status.p);
+    Staging io(c, {{n * 81, order, d_order}, {n * 81, in, d_in, d_out, out}, {n, nullptr, nullptr, d_status, status}});
+    if ((rc = io.send()) || (rc = launch_minimize(c, d_in, d_order, d_out, d_status, n))) return rc;
+    return io.fetch();
 }
 
 int sdk_count_solutions(sdk_ctx* c, const uint8_t* board, uint64_t limit, uint64_t* count, int8_t* status) {
