@@ -57,6 +57,7 @@ SDK_OPT_PROP32_MIN = 27
 SDK_OPT_PROP32_UNDECIDED = 28
 SDK_OPT_PROP32_HANDOVER = 29
 SDK_OPT_PROP32_TAIL = 30
+SDK_OPT_GEN_CAP = 31
 SDK_DONATE_CONTEXT = -1    # sdk_solve_batch_ex: use the context's SDK_OPT_DONATE
 SDK_CHECK_REG1 = 0
 SDK_CHECK_REG2 = 1
@@ -111,6 +112,10 @@ SIGNATURES = {
     "sdk_classify_batch_dev": (ctypes.c_int, [_vp, _vp, _vp, _vp, _sz, ctypes.c_uint64]),
     "sdk_minimize_batch": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _sz]),
     "sdk_minimize_batch_dev": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _sz]),
+    "sdk_generate_grids": (ctypes.c_int, [_vp, ctypes.c_uint64, ctypes.c_uint64, _sz, _vp, _vp, _vp]),
+    "sdk_generate_grids_dev": (ctypes.c_int, [_vp, ctypes.c_uint64, ctypes.c_uint64, _sz, _vp, _vp, _vp]),
+    "sdk_generate_puzzles": (ctypes.c_int, [_vp, ctypes.c_uint64, ctypes.c_uint64, _sz, _vp, _vp, _vp]),
+    "sdk_generate_puzzles_dev": (ctypes.c_int, [_vp, ctypes.c_uint64, ctypes.c_uint64, _sz, _vp, _vp, _vp]),
     "sdk_frontier_boards_dev": (ctypes.c_int, [_vp, ctypes.POINTER(_vp), ctypes.POINTER(ctypes.c_uint64)]),
     "sdk_frontier_load_dev": (ctypes.c_int, [_vp, _vp, ctypes.c_uint64]),
     "sdk_frontier_refine_range": (ctypes.c_int, [_vp, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64,

@@ -18,6 +18,9 @@
  * branching, SDK_ORDER_LEX); tools/make_hard_set.py keeps the puzzles that need >= 20
  * and commits their indices and clue masks.  gen_grid_batch rebuilds the grids of
  * given indices (step 1 alone), so a puzzle is grid & mask without a removal pass.
+ * gen_grid_order_batch gives, beside the grid, the removal order step 2 draws and the fill's
+ * placement count (digits written into a cell): the oracle of the GPU generator
+ * (generate_kernel.h), which reproduces both byte for byte.
  *
  * build: csrc/Makefile (gcc -O2 -shared -fPIC -pthread -> ../libsudoku_gen.so)
  */
@@ -77,7 +80,8 @@ static int count(st_t *s, int limit)
     return total;
 }
 
-static int fill(st_t *s, int i, uint64_t *rng)
+/* *placed counts the digits written into a cell */
+static int fill(st_t *s, int i, uint64_t *rng, uint32_t *placed)
 {
     if (i == 81) return 1;
     uint16_t c = (uint16_t)(ALL & ~(s->row[i / 9] | s->col[i % 9] | s->box[bx(i)]));
@@ -91,27 +95,48 @@ static int fill(st_t *s, int i, uint64_t *rng)
     for (int k = 0; k < n; ++k) {
         uint16_t m = (uint16_t)(1u << d[k]);
         s->row[i / 9] |= m; s->col[i % 9] |= m; s->box[bx(i)] |= m; s->cell[i] = d[k];
-        if (fill(s, i + 1, rng)) return 1;
+        ++*placed;
+        if (fill(s, i + 1, rng, placed)) return 1;
         s->row[i / 9] &= (uint16_t)~m; s->col[i % 9] &= (uint16_t)~m; s->box[bx(i)] &= (uint16_t)~m; s->cell[i] = 0;
     }
     return 0;
 }
 
-void gen_minimal_one(uint64_t seed, uint64_t k, uint8_t *puzzle, uint8_t *solution)
+/* the stream of puzzle k */
+static inline uint64_t stream_of(uint64_t seed, uint64_t k)
 {
-    uint64_t rng = seed * 0x100000001B3ull ^ (k + 1) * 0x9E3779B97F4A7C15ull;
+    return seed * 0x100000001B3ull ^ (k + 1) * 0x9E3779B97F4A7C15ull;
+}
+
+/* step 1: the complete grid; returns the fill's placement count */
+static uint32_t fill_grid(uint64_t *rng, uint8_t *grid)
+{
     st_t s;
     uint8_t zero[81] = {0};
+    uint32_t placed = 0;
     st_init(&s, zero);
-    fill(&s, 0, &rng);
-    memcpy(solution, s.cell, 81);
-    uint8_t b[81], order[81];
-    memcpy(b, s.cell, 81);
+    fill(&s, 0, rng, &placed);
+    memcpy(grid, s.cell, 81);
+    return placed;
+}
+
+/* the removal order: a Fisher-Yates permutation of the cells, from the stream the fill left */
+static void draw_order(uint64_t *rng, uint8_t *order)
+{
     for (int i = 0; i < 81; ++i) order[i] = (uint8_t)i;
     for (int i = 80; i > 0; --i) {
-        int j = (int)(splitmix(&rng) % (uint64_t)(i + 1));
+        int j = (int)(splitmix(rng) % (uint64_t)(i + 1));
         uint8_t t = order[i]; order[i] = order[j]; order[j] = t;
     }
+}
+
+void gen_minimal_one(uint64_t seed, uint64_t k, uint8_t *puzzle, uint8_t *solution)
+{
+    uint64_t rng = stream_of(seed, k);
+    fill_grid(&rng, solution);
+    uint8_t b[81], order[81];
+    memcpy(b, solution, 81);
+    draw_order(&rng, order);
     for (int q = 0; q < 81; ++q) {
         int i = order[q];
         uint8_t v = b[i];
@@ -126,12 +151,23 @@ void gen_minimal_one(uint64_t seed, uint64_t k, uint8_t *puzzle, uint8_t *soluti
 /* the grid of puzzle k (step 1 of gen_minimal_one, same PRNG stream) */
 void gen_grid_one(uint64_t seed, uint64_t k, uint8_t *solution)
 {
-    uint64_t rng = seed * 0x100000001B3ull ^ (k + 1) * 0x9E3779B97F4A7C15ull;
-    st_t s;
-    uint8_t zero[81] = {0};
-    st_init(&s, zero);
-    fill(&s, 0, &rng);
-    memcpy(solution, s.cell, 81);
+    uint64_t rng = stream_of(seed, k);
+    fill_grid(&rng, solution);
+}
+
+/* steps 1 and the order of step 2 of gen_minimal_one: the grid, the removal order and the
+   fill's placement count (each nullable) */
+void gen_grid_order_one(uint64_t seed, uint64_t k, uint8_t *grid, uint8_t *order, uint32_t *placements)
+{
+    uint64_t rng = stream_of(seed, k);
+    uint8_t g[81], o[81];
+    const uint32_t placed = fill_grid(&rng, g);
+    if (grid) memcpy(grid, g, 81);
+    if (order) {
+        draw_order(&rng, o);
+        memcpy(order, o, 81);
+    }
+    if (placements) *placements = placed;
 }
 
 /* ---- search nodes of a singles-propagating lowest-open-cell DFS (the hard filter) ---- */
@@ -216,7 +252,7 @@ uint32_t lex_singles_nodes(const uint8_t *puzzle, uint32_t cap)
     return (uint32_t)nodes;
 }
 
-enum { JOB_MINIMAL, JOB_NODES, JOB_GRIDS };
+enum { JOB_MINIMAL, JOB_NODES, JOB_GRIDS, JOB_GRID_ORDERS };
 typedef struct {
     int kind;
     uint64_t seed, first;
@@ -224,6 +260,7 @@ typedef struct {
     size_t n;
     uint8_t *p, *s;
     uint32_t *nodes;
+    uint8_t *order;
     _Atomic size_t next;
 } job_t;
 
@@ -235,6 +272,9 @@ static void *worker(void *arg)
         if (i >= j->n) break;
         if (j->kind == JOB_GRIDS) {
             gen_grid_one(j->seed, j->idx[i], j->s + 81 * i);
+        } else if (j->kind == JOB_GRID_ORDERS) {
+            gen_grid_order_one(j->seed, j->idx[i], j->s ? j->s + 81 * i : NULL, j->order ? j->order + 81 * i : NULL,
+                               j->nodes ? j->nodes + i : NULL);
         } else if (j->kind == JOB_MINIMAL) {
             gen_minimal_one(j->seed, j->first + i, j->p + 81 * i, j->s + 81 * i);
         } else {
@@ -260,20 +300,28 @@ static int run(job_t *j, int threads)
 /* puzzles k = first .. first+n-1 of seed `seed`, `threads` threads */
 int gen_minimal_batch(uint64_t seed, uint64_t first, size_t n, uint8_t *puzzles, uint8_t *solutions, int threads)
 {
-    job_t j = {JOB_MINIMAL, seed, first, NULL, n, puzzles, solutions, NULL, 0};
+    job_t j = {JOB_MINIMAL, seed, first, NULL, n, puzzles, solutions, NULL, NULL, 0};
     return run(&j, threads);
 }
 
 /* puzzles k = first .. first+n-1 and the singles-DFS search nodes of each (capped at 2^20) */
 int gen_minimal_nodes_batch(uint64_t seed, uint64_t first, size_t n, uint8_t *puzzles, uint32_t *nodes, int threads)
 {
-    job_t j = {JOB_NODES, seed, first, NULL, n, puzzles, NULL, nodes, 0};
+    job_t j = {JOB_NODES, seed, first, NULL, n, puzzles, NULL, nodes, NULL, 0};
     return run(&j, threads);
 }
 
 /* the grids of puzzles idx[0..n-1] */
 int gen_grid_batch(uint64_t seed, const uint64_t *idx, size_t n, uint8_t *grids, int threads)
 {
-    job_t j = {JOB_GRIDS, seed, 0, idx, n, NULL, grids, NULL, 0};
+    job_t j = {JOB_GRIDS, seed, 0, idx, n, NULL, grids, NULL, NULL, 0};
+    return run(&j, threads);
+}
+
+/* the grids, removal orders and fill placement counts of puzzles idx[0..n-1] (each output nullable) */
+int gen_grid_order_batch(uint64_t seed, const uint64_t *idx, size_t n, uint8_t *grids, uint8_t *orders,
+                         uint32_t *placements, int threads)
+{
+    job_t j = {JOB_GRID_ORDERS, seed, 0, idx, n, NULL, grids, placements, orders, 0};
     return run(&j, threads);
 }

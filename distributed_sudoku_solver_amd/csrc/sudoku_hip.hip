@@ -25,6 +25,7 @@
 #include "solve4_kernel.h"   // constants only: the kernel lives in solve4_launch.hip
 #include "prop32_kernel.h"   // constants only: the kernel lives in prop32_launch.hip
 #include "minimize_kernel.h"
+#include "generate_kernel.h"
 #define SDK_DEFINE_LANE_KERNEL
 #include "solve_lane_kernel.h"
 
@@ -381,6 +382,9 @@ struct sdk_ctx {
     uint32_t p32_stamp_wgs = 0;
     DevBuf mz_cand, mz_out, mz_st; // sdk_minimize_batch: a round's candidates, their classify outputs and verdicts
     DevBuf mz_order;               // ... the host-pointer call's order rows
+    int64_t gen_cap = 1 << 20;     // SDK_OPT_GEN_CAP: a generated grid is kept iff its fill placed at most this many digits
+    DevBuf gen_order;              // sdk_generate_puzzles: a slice's removal orders
+    DevBuf gen_plc;                // sdk_generate_grids (host pointers): the placement counts
     DevBuf fr_a, fr_b, prop, bcell, bmask, nchild, offs, fr_status, fr_mask, tsum, fr_ctl;
     DevBuf fr_tail;                // refine_head: the boards kept after the refined ones
     // the device-resident frontier of the last sdk_frontier_build (in fr_a)
@@ -1075,6 +1079,65 @@ int launch_minimize(sdk_ctx* c, const uint8_t* d_in, const uint8_t* d_order, uin
     return span.end(rc);
 }
 
+// Random complete grids (sdk_generate_grids; generate_kernel.h): rows [0, n) are stream indices
+// first .. first + n - 1 of `seed`; the removal orders and placement counts are optional.  One
+// persistent launch per slice of kDnCapBoards rows (the dequeue counter is 32 bits wide).  Under
+// SDK_OPT_TIMING the call is one span (nothing of its own under an outer span).
+int launch_generate(sdk_ctx* c, uint64_t seed, uint64_t first, size_t n, uint8_t* d_grids, uint8_t* d_order,
+                    uint32_t* d_plc) {
+    if (n == 0) return SDK_OK;
+    int rc;
+    if ((rc = ensure(c->counter, 256))) return rc;
+    TimedSpan span(c);
+    if ((rc = span.begin())) return rc;
+    for (uint64_t b0 = 0; b0 < n; b0 += kDnCapBoards) {
+        const uint64_t m = std::min<uint64_t>(n - b0, kDnCapBoards);
+        sdk::GenArgs a{};
+        a.seed_mul = seed * 0x100000001B3ull;
+        a.first = first + b0;
+        a.n = (uint32_t)m;
+        a.cap = (uint32_t)c->gen_cap;
+        a.hard = std::max(a.cap, sdk::kGenFloor);
+        a.grids = d_grids + b0 * 81;
+        a.order = d_order ? d_order + b0 * 81 : nullptr;
+        a.placements = d_plc ? d_plc + b0 : nullptr;
+        a.next = static_cast<uint32_t*>(c->counter.p);
+        HIPCALL(hipMemsetAsync(c->counter.p, 0, 8, c->stream));
+        sdk::generate_kernel<<<grid_for(c, m, sdk::kGenThreads, sdk::kGenWavesPerCu), sdk::kGenThreads, 0, c->stream>>>(a);
+        HIPCALL(hipGetLastError());
+    }
+    return span.end(SDK_OK);
+}
+
+// Minimal puzzles (sdk_generate_puzzles): per slice of kDnCapBoards rows, the grids and their
+// removal orders (into the context's gen_order), then the minimiser over them -- make_minimal's
+// rows, all enqueued without the host.  One span under SDK_OPT_TIMING.
+int launch_generate_puzzles(sdk_ctx* c, uint64_t seed, uint64_t first, size_t n, uint8_t* d_puzzles, uint8_t* d_grids,
+                            int8_t* d_status) {
+    if (n == 0) return SDK_OK;
+    if ((reinterpret_cast<uintptr_t>(d_puzzles) | reinterpret_cast<uintptr_t>(d_grids)) & 15u)
+        return fail(SDK_EINVAL, "device boards must be 16-byte aligned");
+    int rc;
+    if ((rc = ensure(c->gen_order, std::min<uint64_t>(n, kDnCapBoards) * 81))) return rc;
+    uint8_t* d_order = static_cast<uint8_t*>(c->gen_order.p);
+    TimedSpan span(c);
+    if ((rc = span.begin())) return rc;
+    for (uint64_t b0 = 0; b0 < n && !rc; b0 += kDnCapBoards) {
+        const uint64_t m = std::min<uint64_t>(n - b0, kDnCapBoards);
+        if ((rc = launch_generate(c, seed, first + b0, m, d_grids + b0 * 81, d_order, nullptr))) break;
+        rc = launch_minimize(c, d_grids + b0 * 81, d_order, d_puzzles + b0 * 81, d_status + b0, m);
+    }
+    return span.end(rc);
+}
+
+// argument checks of the four generate calls
+int check_generate_args(uint64_t first, size_t n) {
+    int rc;
+    if ((rc = check_board_count(n))) return rc;
+    if (first > UINT64_MAX - (uint64_t)n) return fail(SDK_EINVAL, "first + n overflows the stream index");
+    return SDK_OK;
+}
+
 // Deterministic breadth-first frontier of one board, left in c->fr_a.
 // Every rank that builds it from the same board gets the same boards in the same
 // order, so ranks can split it without exchanging boards.
@@ -1532,6 +1595,10 @@ int sdk_set_option(sdk_ctx* c, int key, int64_t value) {
             if (value != 0 && value != 1) return fail(SDK_EINVAL, "xcd heads must be 0 or 1");
             c->xcd_heads = (int)value;
             return SDK_OK;
+        case SDK_OPT_GEN_CAP:
+            if (value < 81 || value > 0x7FFFFFFFll) return fail(SDK_EINVAL, "SDK_OPT_GEN_CAP must be 81..2^31-1");
+            c->gen_cap = value;
+            return SDK_OK;
         case SDK_OPT_CHECK_VARIANT:
             if (value < SDK_CHECK_REG1 || value > SDK_CHECK_WAVE2) return fail(SDK_EINVAL, "bad check variant %lld", (long long)value);
             c->check_variant = (int)value;
@@ -1678,6 +1745,7 @@ int sdk_get_option(sdk_ctx* c, int key, int64_t* value) {
         case SDK_OPT_PROP32: *value = c->prop32; return SDK_OK;
         case SDK_OPT_PROP32_LC: *value = c->prop32_lc; return SDK_OK;
         case SDK_OPT_PROP32_MIN: *value = c->prop32_min; return SDK_OK;
+        case SDK_OPT_GEN_CAP: *value = c->gen_cap; return SDK_OK;
         case SDK_OPT_PROP32_HANDOVER: *value = c->prop32_handover; return SDK_OK;
         case SDK_OPT_PROP32_TAIL: *value = c->prop32_tail_live | (c->prop32_tail_step << 8); return SDK_OK;
         case SDK_OPT_PROP32_UNDECIDED: {
@@ -1965,6 +2033,73 @@ int sdk_minimize_batch(sdk_ctx* c, const uint8_t* in, const uint8_t* order, uint
     int8_t* d_status = static_cast<int8_t*>(c->status.p);
     Staging io(c, {{n * 81, order, d_order}, {n * 81, in, d_in, d_out, out}, {n, nullptr, nullptr, d_status, status}});
     if ((rc = io.send()) || (rc = launch_minimize(c, d_in, d_order, d_out, d_status, n))) return rc;
+    return io.fetch();
+}
+
+int sdk_generate_grids_dev(sdk_ctx* c, uint64_t seed, uint64_t first, size_t n, void* d_grids, void* d_order,
+                           void* d_placements) {
+    if (!c || (n && !d_grids)) return fail(SDK_EINVAL, "NULL argument");
+    int rc;
+    if ((rc = check_generate_args(first, n))) return rc;
+    if (n == 0) return SDK_OK;
+    if ((reinterpret_cast<uintptr_t>(d_grids) | reinterpret_cast<uintptr_t>(d_order)) & 15u)
+        return fail(SDK_EINVAL, "device boards must be 16-byte aligned");
+    if (reinterpret_cast<uintptr_t>(d_placements) & 3u) return fail(SDK_EINVAL, "d_placements must be 4-byte aligned");
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCALL(hipSetDevice(c->device));
+    return launch_generate(c, seed, first, n, static_cast<uint8_t*>(d_grids), static_cast<uint8_t*>(d_order),
+                           static_cast<uint32_t*>(d_placements));
+}
+
+int sdk_generate_grids(sdk_ctx* c, uint64_t seed, uint64_t first, size_t n, uint8_t* grids, uint8_t* order,
+                       uint32_t* placements) {
+    if (!c || (n && !grids)) return fail(SDK_EINVAL, "NULL argument");
+    int rc;
+    if ((rc = check_generate_args(first, n))) return rc;
+    if (n == 0) return SDK_OK;
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCALL(hipSetDevice(c->device));
+    if ((rc = ensure(c->out, n * 81)) || (order && (rc = ensure(c->mz_order, n * 81))) ||
+        (placements && (rc = ensure(c->gen_plc, n * 4))))
+        return rc;
+    uint8_t* d_grids = static_cast<uint8_t*>(c->out.p);
+    uint8_t* d_order = order ? static_cast<uint8_t*>(c->mz_order.p) : nullptr;
+    uint32_t* d_plc = placements ? static_cast<uint32_t*>(c->gen_plc.p) : nullptr;
+    Staging io(c, {{placements ? n * 4 : 0, nullptr, nullptr, d_plc, placements},
+                   {n * 81, nullptr, nullptr, d_grids, grids},
+                   {order ? n * 81 : 0, nullptr, nullptr, d_order, order}});
+    if ((rc = launch_generate(c, seed, first, n, d_grids, d_order, d_plc))) return rc;
+    return io.fetch();
+}
+
+int sdk_generate_puzzles_dev(sdk_ctx* c, uint64_t seed, uint64_t first, size_t n, void* d_puzzles, void* d_grids,
+                             void* d_status) {
+    if (!c || (n && (!d_puzzles || !d_grids || !d_status))) return fail(SDK_EINVAL, "NULL argument");
+    int rc;
+    if ((rc = check_generate_args(first, n))) return rc;
+    if (n == 0) return SDK_OK;
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCALL(hipSetDevice(c->device));
+    return launch_generate_puzzles(c, seed, first, n, static_cast<uint8_t*>(d_puzzles), static_cast<uint8_t*>(d_grids),
+                                   static_cast<int8_t*>(d_status));
+}
+
+int sdk_generate_puzzles(sdk_ctx* c, uint64_t seed, uint64_t first, size_t n, uint8_t* puzzles, uint8_t* grids,
+                         int8_t* status) {
+    if (!c || (n && (!puzzles || !grids || !status))) return fail(SDK_EINVAL, "NULL argument");
+    int rc;
+    if ((rc = check_generate_args(first, n))) return rc;
+    if (n == 0) return SDK_OK;
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCALL(hipSetDevice(c->device));
+    if ((rc = ensure(c->in, n * 81)) || (rc = ensure(c->out, n * 81)) || (rc = ensure(c->status, n))) return rc;
+    uint8_t* d_grids = static_cast<uint8_t*>(c->in.p);
+    uint8_t* d_puzzles = static_cast<uint8_t*>(c->out.p);
+    int8_t* d_status = static_cast<int8_t*>(c->status.p);
+    Staging io(c, {{n * 81, nullptr, nullptr, d_puzzles, puzzles},
+                   {n * 81, nullptr, nullptr, d_grids, grids},
+                   {n, nullptr, nullptr, d_status, status}});
+    if ((rc = launch_generate_puzzles(c, seed, first, n, d_puzzles, d_grids, d_status))) return rc;
     return io.fetch();
 }
 

@@ -11,6 +11,7 @@ import threading
 import numpy as np
 
 from . import _lib as L
+from . import synth
 
 ALL_DIGITS_MASK = 0x3FE  # bits 1..9: range(1, 10)
 INERT_VALUE = 10         # any given that is never equal to a digit 1..9
@@ -160,7 +161,7 @@ class SudokuEngine:
                      L.SDK_OPT_SOLVER, L.SDK_OPT_WAVES_PER_CU2, L.SDK_OPT_SOLVE_CHUNK, L.SDK_OPT_LOCKED,
                      L.SDK_OPT_XCD_HEADS, L.SDK_OPT_DONATE, L.SDK_OPT_DONATE_MODE, L.SDK_OPT_DONATE_MAX,
                      L.SDK_OPT_DONATE_HELPERS, L.SDK_OPT_DONATE_RESUME, L.SDK_OPT_PROP32, L.SDK_OPT_PROP32_LC,
-                     L.SDK_OPT_PROP32_MIN, L.SDK_OPT_PROP32_HANDOVER, L.SDK_OPT_PROP32_TAIL)
+                     L.SDK_OPT_PROP32_MIN, L.SDK_OPT_PROP32_HANDOVER, L.SDK_OPT_PROP32_TAIL, L.SDK_OPT_GEN_CAP)
 
     def fork(self):
         """A second engine on the same device with its own context and stream (same options):
@@ -330,6 +331,42 @@ class SudokuEngine:
         L.check(self.lib.sdk_minimize_batch(self.ctx, _ptr(boards), _ptr(order), _ptr(out), _ptr(status), n),
                 "sdk_minimize_batch")
         return out, status
+
+    @staticmethod
+    def _stream_rows(n, seed, lo):
+        n, seed, lo = int(n), int(seed), int(lo)
+        if n < 0 or not 0 <= seed < (1 << 64) or not 0 <= lo < (1 << 64):
+            raise ValueError("n must be >= 0, seed and lo unsigned 64-bit integers")
+        return n, seed, lo
+
+    def generate_grids(self, n, seed=synth.DEFAULT_SEED + 3, lo=0, want_order=False, want_placements=False):
+        """Rows [lo, lo+n) of the stream of random complete grids, made on the GPU (sdk_generate_grids):
+        (grids uint8[n,81], order, placements).  Row k depends only on (seed, k): the grids are
+        synth.minimal_grids's, and with want_order / want_placements (else None) the cell orders
+        uint8[n,81] and fill placement counts uint32[n] are synth.grid_orders's, byte for byte.  A
+        grid whose fill places more than SDK_OPT_GEN_CAP digits comes back as zeros with the count
+        0xFFFFFFFF."""
+        n, seed, lo = self._stream_rows(n, seed, lo)
+        grids = np.empty((n, 81), dtype=np.uint8)
+        order = np.empty((n, 81), dtype=np.uint8) if want_order else None
+        placements = np.empty(n, dtype=np.uint32) if want_placements else None
+        L.check(self.lib.sdk_generate_grids(self.ctx, seed, lo, n, _ptr(grids), _ptr(order), _ptr(placements)),
+                "sdk_generate_grids")
+        return grids, order, placements
+
+    def generate_batch(self, n, seed=synth.DEFAULT_SEED + 3, lo=0):
+        """Rows [lo, lo+n) of the stream of minimal unique puzzles, made on the GPU
+        (sdk_generate_puzzles: generate_grids, then minimize_batch in the grids' own removal orders):
+        (puzzles uint8[n,81], solutions uint8[n,81], status int8[n]).  puzzles and solutions are
+        exactly synth.make_minimal(n, seed, lo); status is SDK_SOLVED for every row (a grid dropped
+        by SDK_OPT_GEN_CAP is SDK_MULTIPLE, zeros in both)."""
+        n, seed, lo = self._stream_rows(n, seed, lo)
+        puzzles = np.empty((n, 81), dtype=np.uint8)
+        grids = np.empty((n, 81), dtype=np.uint8)
+        status = np.empty(n, dtype=np.int8)
+        L.check(self.lib.sdk_generate_puzzles(self.ctx, seed, lo, n, _ptr(puzzles), _ptr(grids), _ptr(status)),
+                "sdk_generate_puzzles")
+        return puzzles, grids, status
 
     def expand(self, boards, masks=None, target=64):
         """Lex-ordered frontier below `boards` (sdk_expand_boards): uint8[k,81], children in the
@@ -510,3 +547,14 @@ class SudokuEngine:
         """The order rows are not validated on this path (see include/sudoku_hip.h)."""
         L.check(self.lib.sdk_minimize_batch_dev(self.ctx, d_in.ptr, d_order.ptr, d_out.ptr, d_status.ptr, int(n)),
                 "sdk_minimize_batch_dev")
+
+    def generate_grids_dev(self, d_grids, n, seed=synth.DEFAULT_SEED + 3, lo=0, d_order=None, d_placements=None):
+        L.check(self.lib.sdk_generate_grids_dev(self.ctx, int(seed), int(lo), int(n), d_grids.ptr,
+                                                d_order.ptr if d_order else None,
+                                                d_placements.ptr if d_placements else None),
+                "sdk_generate_grids_dev")
+
+    def generate_batch_dev(self, d_puzzles, d_grids, d_status, n, seed=synth.DEFAULT_SEED + 3, lo=0):
+        L.check(self.lib.sdk_generate_puzzles_dev(self.ctx, int(seed), int(lo), int(n), d_puzzles.ptr, d_grids.ptr,
+                                                  d_status.ptr),
+                "sdk_generate_puzzles_dev")

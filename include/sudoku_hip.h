@@ -44,6 +44,7 @@ extern "C" {
 
 #define SDK_ABI_VERSION 2   /* 2: sdk_solve_batch_ex, frontier records, p2p send/recv; version 2 */
                             /* also gained sdk_classify_batch[_dev] and sdk_minimize_batch[_dev]  */
+                            /* and sdk_generate_grids[_dev] / sdk_generate_puzzles[_dev]          */
                             /* (new symbols only: nothing a version-2 caller uses changed)        */
 
 /* return codes */
@@ -137,6 +138,9 @@ extern "C" {
 #define SDK_OPT_PROP32_TAIL  30  /* ... live | step << 8: from `step` on, a 64-board     */
                                  /* group with at most `live` boards still open hands     */
                                  /* them to the search (0 = never)                       */
+#define SDK_OPT_GEN_CAP      31  /* sdk_generate_*: a grid is kept iff its fill placed at   */
+                                 /* most this many digits, 81..2^31-1 (default 2^20; the   */
+                                 /* heaviest fill of 5 M grids placed 935)                  */
 
 #define SDK_CHECK_REG1       0  /* 1 tile ahead, staged in VGPRs (check_kernel)        */
 #define SDK_CHECK_REG2       1  /* 2 tiles ahead, VGPR ring (check_kernel_rr2)         */
@@ -242,6 +246,35 @@ int sdk_classify_batch(sdk_ctx *ctx, const uint8_t *in, uint8_t *out, int8_t *st
  * launch each, enqueued without the host.  Any n up to 2^31-1 (slices of 2^24 boards). */
 int sdk_minimize_batch(sdk_ctx *ctx, const uint8_t *in, const uint8_t *order, uint8_t *out,
                        int8_t *status, size_t n);
+
+/* Random complete grids, made on the GPU (generate_kernel.h, one grid per lane).  Row i is stream
+ * index k = first + i of `seed`: the grid a randomised row-major backtracking fill gives under the
+ * splitmix64 stream of (seed, k) -- a pure function of (seed, k), the grid of the host generator
+ * (csrc/gen_minimal.c gen_grid_one; synth.minimal_grids), byte for byte.
+ *   grids       uint8[n][81].
+ *   order       nullable, uint8[n][81]: the permutation of 0..80 the same stream draws after the
+ *               fill -- the cell order in which the host generator removes clues.
+ *   placements  nullable, uint32[n]: digits the fill wrote into cells (81 = it never took one back).
+ * A grid whose fill places more than SDK_OPT_GEN_CAP digits is not kept: its row is 81 zeros and its
+ * count 0xFFFFFFFF.  Its order row is the stream's all the same (the order continues the stream
+ * where the fill leaves it, so the fill is still followed to its end); the fill itself, and with it
+ * every loop of the kernel, stops at max(SDK_OPT_GEN_CAP, 2^20) placements, after which the order is
+ * drawn from the stream as it stands.  first + n must not overflow; any n up to 2^31-1 (slices of
+ * 2^24 rows).  Under SDK_OPT_TIMING a call records one span, whatever its slices. */
+int sdk_generate_grids(sdk_ctx *ctx, uint64_t seed, uint64_t first, size_t n, uint8_t *grids,
+                       uint8_t *order, uint32_t *placements);
+
+/* Minimal unique puzzles, made on the GPU: the grids of sdk_generate_grids, then sdk_minimize_batch
+ * over them in their own removal orders (kept in a context buffer), all enqueued without the host.
+ * Row i is the host generator's puzzle first + i (gen_minimal_one; synth.make_minimal) with its
+ * grid, byte for byte.
+ *   puzzles  uint8[n][81];  grids  uint8[n][81], the puzzles' completions;
+ *   status   the minimiser's: SDK_SOLVED for every grid that was kept.  A grid that was not (see
+ *            SDK_OPT_GEN_CAP) is 81 zeros: SDK_MULTIPLE, and its puzzle row is 81 zeros too.
+ * All three are required.  Under SDK_OPT_TIMING a call records one span (the generate launches and
+ * the minimise rounds of all its slices). */
+int sdk_generate_puzzles(sdk_ctx *ctx, uint64_t seed, uint64_t first, size_t n, uint8_t *puzzles,
+                         uint8_t *grids, int8_t *status);
 
 /* The worklist step of a resumable lex-first search of a board whose solve hit the
  * budget (distributed_sudoku_solver_amd/search.py; the in-node form of handing a
@@ -394,6 +427,12 @@ int sdk_classify_batch_dev(sdk_ctx *ctx, const void *d_in, void *d_out, void *d_
  * repeated cell is tried again (a no-op: it is empty, or it could not go). */
 int sdk_minimize_batch_dev(sdk_ctx *ctx, const void *d_in, const void *d_order, void *d_out,
                            void *d_status, size_t n);
+/* d_grids (and d_order, d_puzzles) 16-byte aligned, else SDK_EINVAL; d_order and d_placements
+ * (uint32[n]) nullable.  Spans as the host-pointer forms: one per call. */
+int sdk_generate_grids_dev(sdk_ctx *ctx, uint64_t seed, uint64_t first, size_t n, void *d_grids,
+                           void *d_order, void *d_placements);
+int sdk_generate_puzzles_dev(sdk_ctx *ctx, uint64_t seed, uint64_t first, size_t n, void *d_puzzles,
+                             void *d_grids, void *d_status);
 
 /* Kernel time accounting (HIP events on the context stream, bracketing every
  * kernel launched by the *_dev / host calls since the last reset).  Only with
