@@ -24,6 +24,13 @@ SDK_BUDGET_HIT = -2
 SDK_MULTIPLE = 2      # sdk_classify_batch / sdk_minimize_batch only: at least two completions
 SDK_BUDGET_CONTEXT = (1 << 64) - 1    # sdk_solve_batch_budget: use the context's SDK_OPT_NODE_BUDGET
 
+# sdk_grade_batch levels: the technique set a board needs (0: not uniquely solvable / givens not clean)
+SDK_GRADE_NONE = 0
+SDK_GRADE_NAKED = 1
+SDK_GRADE_HIDDEN = 2
+SDK_GRADE_LOCKED = 3
+SDK_GRADE_SEARCH = 4
+
 SDK_CHECK_OK = 1
 SDK_CHECK_RAW_NAMEERROR = 2
 
@@ -110,6 +117,8 @@ SIGNATURES = {
     "sdk_solve_batch_ex": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, ctypes.c_uint64, ctypes.c_int64]),
     "sdk_classify_batch": (ctypes.c_int, [_vp, _vp, _vp, _vp, _sz, ctypes.c_uint64]),
     "sdk_classify_batch_dev": (ctypes.c_int, [_vp, _vp, _vp, _vp, _sz, ctypes.c_uint64]),
+    "sdk_grade_batch": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, ctypes.c_uint64]),
+    "sdk_grade_batch_dev": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, ctypes.c_uint64]),
     "sdk_minimize_batch": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _sz]),
     "sdk_minimize_batch_dev": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _sz]),
     "sdk_generate_grids": (ctypes.c_int, [_vp, ctypes.c_uint64, ctypes.c_uint64, _sz, _vp, _vp, _vp]),

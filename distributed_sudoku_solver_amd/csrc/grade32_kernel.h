@@ -1,0 +1,233 @@
+// grade32_kernel.h -- the propagation pass run as a grader: which technique does a board need?
+// (sdk_grade_batch; include/sudoku_hip.h has the contract, DESIGN.md "Grading" the measurements)
+//
+// Same layout and the same device functions as prop32_kernel.h: bit b of a word is board b of the
+// half's 32, lane hl < 27 owns row triad hl and unit hl.  What differs is the schedule.  The fast pass
+// runs naked singles (N), hidden singles (H) and locked candidates (L) together, on a schedule tuned
+// for speed; here every board climbs R1 = {N}, R2 = {N, H}, R3 = {N, H, L} one set at a time and only
+// from a fixpoint of the set it is in, so the set it holds when it is found solved is its level.
+//
+// Per-board technique masks.  Two board masks per group, `hid` and `lck` (64-bit scalars, bit 32 h + b
+// as the pass's other masks; a lane uses its half's word), gate the rules bitwise -- one instruction
+// stream, no divergence, boards of one word at different levels at the same time:
+//   H  p32_cells<true, true>: the `anyh` word of a cell (boards in which the cell has a hidden
+//      single) is ANDed with hid, so c &= H | ~anyh leaves the other boards' words alone;
+//   L  p32_locked only removes from open cells (& ~s): the boards outside lck get their bits set in
+//      the lane's three single words before the call (s is recomputed by the next p32_singles and
+//      the pass reads nothing else of it), so it removes nothing from them.
+// Escalation.  Every cells phase reports change bits.  A live board unchanged by a full step
+//   without hid           gets hid;
+//   with hid, without lck gets lck, and the group's next step is a locked pass;
+//   with lck              -- the group's next step is a locked pass; unchanged by that too: stuck,
+//                         at F_3, listed for the search (a board that just got lck was unchanged by
+//                         the N + H step before the pass, so the same test holds for it).
+// The locked pass also runs on the other lck boards of the group (still R3, and it can only remove).
+// Only live boards escalate, so a decided board keeps the masks it was decided with: level =
+// 1 + hid + lck for a solved board.
+//
+// The step limit is a termination guard only.  Count the unit/cells steps (`it`) a board can be live
+// for: a step either removes at least one of its 729 candidates, or is one of its two escalations, or
+// is an unchanged step under lck -- and that one is followed by a locked pass which removes a
+// candidate (one of the same 729) or ends the board.  So no board sees more than 729 + 3 steps short
+// of F_3; kG32MaxSteps is above that.  (The fast pass's 96 is a hand-off, not a bound.)
+//
+// Open cells.  For a stuck board the number of open cells of its final state: after the loop one
+// p32_singles puts the 81 single words of each half into the cell records, and lane (half, b) --
+// here a board, not a triad -- reads its half's 81 words (every lane of the half the same address: a
+// broadcast, no bank conflict) and counts the clear bits at position b.  81 ds_read_b32 and as many
+// bit extracts per group that has a stuck board, against ~120 LDS instructions per step: cheaper
+// than a bit-sliced adder tree across lanes (seven planes through five DPP stages), and no state.
+//
+// Outputs.  status / out / the undecided list exactly as prop32_kernel (handover, the "digit closed
+// twice" refutation of a handed grid included); level[] for every board: 1..3 solved, 4 stuck
+// (provisional: g32_verdict_kernel clears it unless the search finds exactly one completion), 0
+// refuted or inexact; open[] the count for stuck boards, else 0.
+#pragma once
+#include "prop32_kernel.h"
+
+namespace sdk {
+
+constexpr uint32_t kG32MaxSteps = 768;   // > 729 + 3 (see above)
+
+struct Grade32Args {
+    Prop32Args p;        // in, out, status, n, heads, list, list_in, handover (no schedule, no tail)
+    uint8_t* level;      // [n]
+    uint8_t* open;       // [n]
+};
+
+// SDK_GRADE32_STATS (profiling builds only): per group, histograms of the unit/cells steps it ran and
+// of its locked passes (tools/bench_grade.py --stats reads them)
+#ifndef SDK_GRADE32_STATS
+#define SDK_GRADE32_STATS 0
+#endif
+
+#ifdef SDK_DEFINE_GRADE32_KERNEL
+#if SDK_GRADE32_STATS
+__device__ unsigned long long g_g32_stats[2][128];
+#define G32_STAT(k, v) atomicAdd(&g_g32_stats[k][min((uint32_t)(v), 127u)], 1ull)
+#else
+#define G32_STAT(k, v) ((void)0)
+#endif
+
+// The search's verdicts into the grades: a listed board keeps level 4 and its open count only where
+// the search found exactly one completion (budget hits, several and none: both 0).
+__global__ void g32_verdict_kernel(const uint32_t* list, const int8_t* sub_st, uint8_t* level, uint8_t* open) {
+    const uint32_t m = list[0];
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < m; i += gridDim.x * blockDim.x)
+        if (sub_st[i] != 1) {
+            const uint32_t j = list[1 + i];
+            level[j] = 0;
+            open[j] = 0;
+        }
+}
+
+// the lane's half of a 64-bit board mask
+__device__ __forceinline__ uint32_t g32_word(const P32Lane& w, uint64_t m) {
+    return w.half ? (uint32_t)(m >> 32) : (uint32_t)m;
+}
+
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) void grade32_kernel(Grade32Args ga) {
+    const Prop32Args& a = ga.p;
+    __shared__ __attribute__((aligned(16))) uint8_t s_lds[kP32Lds];
+    p32_lds_t* const lds = (p32_lds_t*)s_lds;
+    p32_order_table(lds);
+    __builtin_amdgcn_wave_barrier();
+    P32Lane w;
+    w.half = threadIdx.x >> 5;
+    w.hl = threadIdx.x & 31;
+    w.act = w.hl < 27;
+    w.reg = lds + w.half * kP32Region;
+    const uint32_t groups = (uint32_t)((a.n + 63) / 64);
+    uint32_t seg = blockIdx.x % kP32Heads;
+    for (;;) {
+        const uint32_t g = p32_dequeue(a, groups, seg);
+        if (g == ~0u) break;
+        const uint64_t base = (uint64_t)g * 64;
+        const uint32_t nb = (uint32_t)min<uint64_t>(64, a.n - base);
+        const uint8_t* src = a.in + base * 81;
+        P32Cells x;
+        uint64_t inert64;
+        {
+            uint32_t d[32];
+            p32_load(src, nb, d);
+            const uint32_t hi = p32_convert(d, x);
+            inert64 = p32_mask64(p32_half_or(w.act ? hi : 0u));
+        }
+        const uint64_t valid = nb >= 64u ? ~0ull : ((1ull << nb) - 1ull);
+        uint64_t undec = inert64 & valid, inexact = undec;
+        uint64_t live = valid & ~undec, solved = 0ull, contra = 0ull;
+        uint64_t hid = 0ull, lck = 0ull;   // the boards' technique masks
+        uint64_t fixl = 0ull;              // lck boards unchanged by the step before this locked pass
+        bool lc = false;
+        uint32_t it = 0;
+#if SDK_GRADE32_STATS
+        uint32_t st_lc = 0;
+#endif
+        // one step; as in prop32_body every path through it ends in an update of the cell words, and
+        // the loop runs two per iteration
+        auto step = [&]() {
+            uint32_t empty, alls;
+            p32_singles(w, x, empty, alls);
+            __builtin_amdgcn_wave_barrier();
+            if (lc) {
+#if SDK_GRADE32_STATS
+                ++st_lc;
+#endif
+                const uint32_t off = ~g32_word(w, lck);    // boards without L: every cell reads as closed
+#pragma unroll
+                for (int k = 0; k < 3; ++k) x.s[k] |= off;
+                const uint32_t lc_own = p32_locked(w, x);
+                const uint64_t lchg = p32_mask64(p32_half_or(w.act ? lc_own : 0u));
+                const uint64_t stuck = fixl & ~lchg & live;
+                undec |= stuck;
+                live &= ~stuck;
+                fixl = 0ull;
+                lc = false;
+                __builtin_amdgcn_wave_barrier();
+                return;
+            }
+            uint32_t miss, dup = 0u;
+            if (it == 0) {   // a digit given twice: not exact, to the search
+                p32_unit<true>(w, lds, miss, dup);
+                const uint64_t dupw = p32_mask64(p32_half_or(w.act ? dup : 0u)) & live;
+                undec |= dupw;
+                inexact |= dupw;
+                live &= ~dupw;
+            } else {
+                p32_unit<false>(w, lds, miss, dup);
+            }
+            const uint64_t badw = p32_mask64(p32_half_or(w.act ? (miss | empty) : 0u));
+            const uint64_t allw = p32_mask64(p32_half_and(w.act ? alls : ~0u));
+            const uint64_t sv = allw & ~badw & live, ct = badw & live;
+            solved |= sv;
+            contra |= ct;
+            live &= ~(sv | ct);
+            if (live != 0ull && ++it >= kG32MaxSteps) {   // (unreachable: see the header)
+                undec |= live;
+                live = 0ull;
+            }
+            __builtin_amdgcn_wave_barrier();
+            const uint32_t chg_own = p32_cells<true, true>(w, x, g32_word(w, hid));
+            const uint64_t unch = live & ~p32_mask64(p32_half_or(w.act ? chg_own : 0u));
+            // at a fixpoint of its set: the next set, or the locked pass that tells whether it is F_3
+            fixl = unch & hid;
+            lck |= fixl;
+            hid |= unch;
+            lc = fixl != 0ull;
+            __builtin_amdgcn_wave_barrier();
+        };
+        while (live != 0ull) {
+            step();
+            if (live == 0ull) break;
+            step();
+        }
+#if SDK_GRADE32_STATS
+        if (threadIdx.x == 0) {
+            G32_STAT(0, it);
+            G32_STAT(1, st_lc);
+        }
+#endif
+        __builtin_amdgcn_wave_barrier();
+        // the stuck boards (undecided, exact): their open cells, and with handover their grids
+        uint64_t stuck = undec & ~inexact;
+        uint64_t handed = a.handover ? stuck : 0ull;
+        uint32_t nopen = 0u;
+        if (stuck) {
+            uint32_t empty, alls;
+            p32_singles(w, x, empty, alls);
+            __builtin_amdgcn_wave_barrier();
+            if (handed) {
+                // two closed cells with one digit in a unit: no completion (prop32_body)
+                const uint64_t dupw = p32_mask64(p32_half_or(w.act ? p32_dups(w, lds) : 0u)) & handed;
+                contra |= dupw;
+                undec &= ~dupw;
+                handed &= ~dupw;
+                stuck &= ~dupw;
+            }
+            // this lane as board (half, hl): the clear bits hl of its half's 81 single words
+            const uint32_t bit = p32_opq(w.hl);
+#pragma unroll 9
+            for (uint32_t j = 0; j < 81u; ++j) {
+                const uint32_t s =
+                    *(const volatile __attribute__((address_space(3))) uint32_t*)(w.reg + kP32Rec * j + 36u);
+                nopen += (~s >> bit) & 1u;
+            }
+            __builtin_amdgcn_wave_barrier();
+        }
+        p32_answers(a, w, x, lds, base, nb, solved, contra, handed);
+        // statuses and grades; the undecided boards are listed for the search
+        const uint32_t me = p32_opq(threadIdx.x);        // board me of the group (32 half + hl)
+        if ((valid >> me) & 1ull) {
+            const bool sv = (solved >> me) & 1ull, st = (stuck >> me) & 1ull;
+            a.status[base + me] = (int8_t)(sv ? 1 : (((contra >> me) & 1ull) ? 0 : kStUndecided));
+            ga.level[base + me] =
+                (uint8_t)(sv ? 1u + (uint32_t)((hid >> me) & 1ull) + (uint32_t)((lck >> me) & 1ull) : (st ? 4u : 0u));
+            ga.open[base + me] = (uint8_t)(st ? nopen : 0u);
+        }
+        p32_list_undecided(a, lds, base, me, undec, handed);
+        __builtin_amdgcn_wave_barrier();
+    }
+}
+#endif
+
+}  // namespace sdk

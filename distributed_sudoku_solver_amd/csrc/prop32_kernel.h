@@ -444,8 +444,9 @@ __device__ __forceinline__ void p32_unit(const P32Lane& w, const p32_lds_t* lds,
 // step before a locked-candidates pass needs them: a board unchanged by it and by the pass is stuck).
 // The lane's cells 3j + k share row j / 3 and box 3 (j / 9) + j % 3: those two records are read once
 // (36 registers for the phase), each cell's column record beside its update.
-template <bool CHG>
-__device__ __forceinline__ uint32_t p32_cells(const P32Lane& w, P32Cells& x) {
+// GATE (the grading pass, grade32_kernel.h): the hidden-single restriction only for the boards of `hid`
+template <bool CHG, bool GATE = false>
+__device__ __forceinline__ uint32_t p32_cells(const P32Lane& w, P32Cells& x, uint32_t hid = ~0u) {
     const uint32_t j = p32_opq(w.hl);
     const uint32_t r = j / 3, bc = j - 3 * r;          // row r, box column bc: columns 3 bc + k
     const uint32_t rowrec = kP32URec * r, boxrec = kP32URec * (18 + 3 * (r / 3) + bc),
@@ -468,6 +469,7 @@ __device__ __forceinline__ uint32_t p32_cells(const P32Lane& w, P32Cells& x) {
             const uint2 c = p32_ld(w.reg, colrec + kP32URec * k + 8 * d);   // column 3 bc + k
             p32_upd1<CHG>(x.c[k][d], H[d], anyh, chg, x.s[k], c.x, rT[d], bT[d], c.y, rW[d], bW[d]);
         }
+        if (GATE) anyh &= hid;
 #pragma unroll
         for (int d = 0; d < 9; ++d) p32_upd2<CHG>(x.c[k][d], H[d], anyh, chg);
     }
@@ -764,6 +766,57 @@ __device__ __forceinline__ uint32_t p32_dequeue(const Prop32Args& a, uint32_t gr
     return ~0u;
 }
 
+// A group's answers (prop32_body and the grading pass, grade32_kernel.h): into the staging the digits
+// of the solved and handed-over boards (binary planes of the one-hot words) and, for boards without a
+// completion, their input (DHT_Node.py:535); then out, for the whole group.
+__device__ __forceinline__ void p32_answers(const Prop32Args& a, const P32Lane& w, const P32Cells& x, p32_lds_t* lds,
+                                            uint64_t base, uint32_t nb, uint64_t solved, uint64_t contra,
+                                            uint64_t handed) {
+    if ((solved | handed) && w.act) p32_digits(x, w.reg + 4u * w.hl);
+    for (uint64_t m = contra; m; m &= m - 1ull) {     // rare: the 81 bytes by 64 lanes
+        const uint32_t p = (uint32_t)__builtin_ctzll(m);
+        const uint8_t* s = a.in + (base + p) * 81;
+        lds[p32_stage_byte(p, threadIdx.x)] = s[threadIdx.x];
+        if (threadIdx.x < 17u) lds[p32_stage_byte(p, 64u + threadIdx.x)] = s[64 + threadIdx.x];
+    }
+    __builtin_amdgcn_wave_barrier();
+    if (solved | contra) {
+        // undecided boards' rows get what the staging holds; the search's answers replace them
+        uint8_t* dst = a.out + base * 81;
+        if (nb == 64) {
+            p32_store_group(lds, dst);
+        } else {
+            for (uint32_t o = threadIdx.x; o < nb * 81u; o += 64u) dst[o] = lds[o + o / 3u];
+        }
+    }
+}
+
+// The group's undecided boards onto the list, with their propagated grids (`handed`: from the staging)
+// or their inputs, dense, in list order; me: the lane as board of the group.
+__device__ __forceinline__ void p32_list_undecided(const Prop32Args& a, const p32_lds_t* lds, uint64_t base,
+                                                   uint32_t me, uint64_t undec, uint64_t handed) {
+    if (undec) {
+        uint32_t k0 = 0;
+        if (threadIdx.x == 0) k0 = atomicAdd(a.list, (uint32_t)__builtin_popcountll(undec));
+        k0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)k0);
+        if ((undec >> me) & 1ull)
+            a.list[1 + k0 + (uint32_t)__builtin_popcountll(undec & ((1ull << me) - 1ull))] = (uint32_t)(base + me);
+        uint32_t k = k0;
+        for (uint64_t m = undec; m; m &= m - 1ull, ++k) {
+            const uint32_t p = (uint32_t)__builtin_ctzll(m);
+            uint8_t* d = a.list_in + (uint64_t)k * 81;
+            if ((handed >> p) & 1ull) {      // the propagated grid, from the staging
+                d[threadIdx.x] = lds[p32_stage_byte(p, threadIdx.x)];
+                if (threadIdx.x < 17u) d[64 + threadIdx.x] = lds[p32_stage_byte(p, 64u + threadIdx.x)];
+            } else {
+                const uint8_t* s = a.in + (base + p) * 81;
+                d[threadIdx.x] = s[threadIdx.x];
+                if (threadIdx.x < 17u) d[64 + threadIdx.x] = s[64 + threadIdx.x];
+            }
+        }
+    }
+}
+
 // SDK_PROP32_STATS (profiling builds only): per group, histograms of the steps it ran, of the step at
 // which at most 4 / at most 1 of its boards were still live, and the locked-candidates passes
 #ifndef SDK_PROP32_STATS
@@ -806,9 +859,12 @@ __global__ void p32_scatter_kernel(const uint32_t* list, const uint8_t* sub_out,
     }
 }
 
+#endif
+
+#if defined(SDK_DEFINE_PROP32_KERNEL) || defined(SDK_DEFINE_GRADE32_KERNEL)
 // kP32Order (see p32_unit): digit class t of a Sudoku solution with cell indices distinct mod 32
-// in every class
-__constant__ uint8_t kP32Order[81] = {2, 5, 8, 1, 4, 7, 3, 0, 6, 1, 4, 7, 0, 3, 6, 2, 8, 5, 0, 3, 6, 8, 2, 5, 1,
+// in every class (static: the grading pass's translation unit, grade32_kernel.h, has its own copy)
+static __constant__ uint8_t kP32Order[81] = {2, 5, 8, 1, 4, 7, 3, 0, 6, 1, 4, 7, 0, 3, 6, 2, 8, 5, 0, 3, 6, 8, 2, 5, 1,
                                       7, 4, 8, 2, 5, 7, 1, 4, 0, 6, 3, 7, 1, 4, 6, 0, 3, 8, 5, 2, 6, 0, 3, 5, 8,
                                       2, 7, 4, 1, 5, 8, 2, 4, 7, 1, 6, 3, 0, 4, 7, 1, 3, 6, 0, 5, 2, 8, 3, 6, 0,
                                       2, 5, 8, 4, 1, 7};
@@ -836,6 +892,9 @@ __device__ __forceinline__ void p32_order_table(p32_lds_t* lds) {
     }
 }
 
+#endif
+
+#ifdef SDK_DEFINE_PROP32_KERNEL
 #ifndef SDK_PROP32_WAVES_PER_EU
 #define SDK_PROP32_WAVES_PER_EU 4
 #endif
@@ -987,47 +1046,12 @@ __device__ __forceinline__ void prop32_body(Prop32Args a, uint64_t* stamps) {
             handed &= ~dupw;
             __builtin_amdgcn_wave_barrier();
         }
-        if ((solved | handed) && w.act) p32_digits(x, w.reg + 4u * w.hl);
-        for (uint64_t m = contra; m; m &= m - 1ull) {     // rare: the 81 bytes by 64 lanes
-            const uint32_t p = (uint32_t)__builtin_ctzll(m);
-            const uint8_t* s = a.in + (base + p) * 81;
-            lds[p32_stage_byte(p, threadIdx.x)] = s[threadIdx.x];
-            if (threadIdx.x < 17u) lds[p32_stage_byte(p, 64u + threadIdx.x)] = s[64 + threadIdx.x];
-        }
-        __builtin_amdgcn_wave_barrier();
-        if (solved | contra) {
-            // undecided boards' rows get what the staging holds; the search's answers replace them
-            uint8_t* dst = a.out + base * 81;
-            if (nb == 64) {
-                p32_store_group(lds, dst);
-            } else {
-                for (uint32_t o = threadIdx.x; o < nb * 81u; o += 64u) dst[o] = lds[o + o / 3u];
-            }
-        }
+        p32_answers(a, w, x, lds, base, nb, solved, contra, handed);
         // statuses; the undecided boards are listed with their inputs for the search
         const uint32_t me = p32_opq(threadIdx.x);        // board me of the group (32 half + hl)
         if ((valid >> me) & 1ull)
             a.status[base + me] = (int8_t)(((solved >> me) & 1ull) ? 1 : (((contra >> me) & 1ull) ? 0 : kStUndecided));
-        if (undec) {
-            uint32_t k0 = 0;
-            if (threadIdx.x == 0) k0 = atomicAdd(a.list, (uint32_t)__builtin_popcountll(undec));
-            k0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)k0);
-            if ((undec >> me) & 1ull)
-                a.list[1 + k0 + (uint32_t)__builtin_popcountll(undec & ((1ull << me) - 1ull))] = (uint32_t)(base + me);
-            uint32_t k = k0;
-            for (uint64_t m = undec; m; m &= m - 1ull, ++k) {
-                const uint32_t p = (uint32_t)__builtin_ctzll(m);
-                uint8_t* d = a.list_in + (uint64_t)k * 81;
-                if ((handed >> p) & 1ull) {      // the propagated grid, from the staging
-                    d[threadIdx.x] = lds[p32_stage_byte(p, threadIdx.x)];
-                    if (threadIdx.x < 17u) d[64 + threadIdx.x] = lds[p32_stage_byte(p, 64u + threadIdx.x)];
-                } else {
-                    const uint8_t* s = a.in + (base + p) * 81;
-                    d[threadIdx.x] = s[threadIdx.x];
-                    if (threadIdx.x < 17u) d[64 + threadIdx.x] = s[64 + threadIdx.x];
-                }
-            }
-        }
+        p32_list_undecided(a, lds, base, me, undec, handed);
         __builtin_amdgcn_wave_barrier();
     }
     if (kStamp) {

@@ -24,6 +24,7 @@
 #include "solve2_kernel.h"   // constants only: the kernel lives in solve2_launch.hip
 #include "solve4_kernel.h"   // constants only: the kernel lives in solve4_launch.hip
 #include "prop32_kernel.h"   // constants only: the kernel lives in prop32_launch.hip
+#include "grade32_kernel.h"  // constants only: the kernel lives in grade32_launch.hip
 #include "minimize_kernel.h"
 #include "generate_kernel.h"
 #define SDK_DEFINE_LANE_KERNEL
@@ -36,6 +37,9 @@ int solve4_dn_blocks_per_cu();   // resident workgroups per CU of solve4_kernel<
 hipError_t launch_prop32(const Prop32Args& a, unsigned grid, hipStream_t stream, uint64_t* stamps);
 hipError_t launch_p32_scatter(const uint32_t* list, const uint8_t* sub_out, const int8_t* sub_st, const uint8_t* in,
                               uint8_t* out, int8_t* status, unsigned grid, hipStream_t stream);
+hipError_t launch_grade32(const Grade32Args& a, unsigned grid, hipStream_t stream);
+hipError_t launch_g32_verdict(const uint32_t* list, const int8_t* sub_st, uint8_t* level, uint8_t* open,
+                              unsigned grid, hipStream_t stream);
 hipError_t launch_expand4(const ExpandArgs& a, unsigned grid, hipStream_t stream);   // expand4_kernel.h
 }
 
@@ -382,6 +386,9 @@ struct sdk_ctx {
     uint32_t p32_stamp_wgs = 0;
     DevBuf mz_cand, mz_out, mz_st; // sdk_minimize_batch: a round's candidates, their classify outputs and verdicts
     DevBuf mz_order;               // ... the host-pointer call's order rows
+    DevBuf gr_in;                  // sdk_grade_batch_dev with d_out == d_in: a slice's inputs
+    DevBuf gr_level, gr_open;      // sdk_grade_batch: the host-pointer call's grades (gr_open also
+                                   // where the caller wants no open counts)
     int64_t gen_cap = 1 << 20;     // SDK_OPT_GEN_CAP: a generated grid is kept iff its fill placed at most this many digits
     DevBuf gen_order;              // sdk_generate_puzzles: a slice's removal orders
     DevBuf gen_plc;                // sdk_generate_grids (host pointers): the placement counts
@@ -1036,6 +1043,72 @@ int launch_classify(sdk_ctx* c, const uint8_t* d_in, uint8_t* d_out, int8_t* d_s
         rc = launch_solve(c, s);
     }
     return rc;
+}
+
+// Grade launch (sdk_grade_batch; grade32_kernel.h): the grading pass over every slice of
+// kDnCapBoards -- always, whatever SDK_OPT_PROP32* and the batch size, since the level is read from
+// it; no tail hand-off (a tail snapshot is not a fixpoint) -- then the boards it lists through the
+// classify search (launch_solve, ORDER_CLASSIFY, the list's length on the device), the usual scatter
+// of their answers and the verdict kernel that keeps level 4 only for "exactly one".  Control words and
+// the list are the prop32 pass's (re-initialised by every call that uses them).  One span under
+// SDK_OPT_TIMING.  d_open null: the counts go to scratch.  d_out == d_in: a slice's inputs are
+// copied aside first (the pass and the scatter read a board's input after its group's output is
+// written).  budget as launch_classify's.  Outcome fields as a classify that ran the pass:
+// prop32_ran (SDK_OPT_PROP32_UNDECIDED counts the last slice's listed boards), dn_ran false.
+int launch_grade(sdk_ctx* c, const uint8_t* d_in, uint8_t* d_out, int8_t* d_status, uint8_t* d_level, uint8_t* d_open,
+                 size_t n, int64_t budget) {
+    if (n == 0) return SDK_OK;
+    if ((reinterpret_cast<uintptr_t>(d_in) | reinterpret_cast<uintptr_t>(d_out)) & 15u)
+        return fail(SDK_EINVAL, "device boards must be 16-byte aligned");
+    if (budget < 0) budget = (int64_t)c->budget;
+    const uint64_t cap = std::min<uint64_t>(n, kDnCapBoards);
+    const bool in_place = d_in == d_out;
+    constexpr size_t kCtlBytes = (size_t)sdk::kP32Heads * sdk::kP32HeadStride * 4;
+    int rc;
+    if ((rc = ensure(c->p32_ctl, kCtlBytes)) || (rc = ensure(c->p32_list, (cap + 1) * 4)) ||
+        (rc = ensure(c->p32_in, cap * 81)) || (rc = ensure(c->p32_out, cap * 81)) || (rc = ensure(c->p32_st, cap)) ||
+        (in_place && (rc = ensure(c->gr_in, cap * 81))) || (!d_open && (rc = ensure(c->gr_open, cap))))
+        return rc;
+    TimedSpan span(c);
+    if ((rc = span.begin())) return rc;
+    for (uint64_t b0 = 0; b0 < n && !rc; b0 += kDnCapBoards) {
+        const uint64_t m = std::min<uint64_t>(n - b0, kDnCapBoards);
+        const uint8_t* in = d_in + b0 * 81;
+        if (in_place) {
+            HIPCALL(hipMemcpyAsync(c->gr_in.p, in, m * 81, hipMemcpyDeviceToDevice, c->stream));
+            in = static_cast<const uint8_t*>(c->gr_in.p);
+        }
+        HIPCALL(hipMemsetAsync(c->p32_ctl.p, 0, kCtlBytes, c->stream));
+        HIPCALL(hipMemsetAsync(c->p32_list.p, 0, 4, c->stream));
+        sdk::Grade32Args a{};
+        a.p.in = in;
+        a.p.out = d_out + b0 * 81;
+        a.p.status = d_status + b0;
+        a.p.n = m;
+        a.p.heads = static_cast<uint32_t*>(c->p32_ctl.p);
+        a.p.list = static_cast<uint32_t*>(c->p32_list.p);
+        a.p.list_in = static_cast<uint8_t*>(c->p32_in.p);
+        // (a budget counts nodes from the input: launch_prop32_solve)
+        a.p.handover = (c->prop32_handover && budget == 0) ? 1 : 0;
+        a.level = d_level + b0;
+        a.open = d_open ? d_open + b0 : static_cast<uint8_t*>(c->gr_open.p);
+        HIPCALL(sdk::launch_grade32(a, grid_for(c, m, 64, 20), c->stream));
+        c->prop32_ran = true;
+        SolveCall rest{a.p.list_in, nullptr, static_cast<uint8_t*>(c->p32_out.p), static_cast<int8_t*>(c->p32_st.p),
+                       nullptr, (size_t)m};
+        rest.n_dev = a.p.list;
+        rest.order = sdk::ORDER_CLASSIFY;
+        rest.solver = SDK_SOLVER_QUAD;
+        rest.budget = budget;
+        rest.donate = 0;
+        if ((rc = launch_solve(c, rest))) break;
+        if (sdk::launch_p32_scatter(rest.n_dev, rest.out, rest.status, a.p.in, a.p.out, a.p.status,
+                                    grid_for(c, m * 81, 1024, 8), c->stream) != hipSuccess ||
+            sdk::launch_g32_verdict(rest.n_dev, rest.status, a.level, a.open, grid_for(c, m, 256, 8), c->stream) !=
+                hipSuccess)
+            rc = fail(SDK_EHIP, "grade scatter launch failed");
+    }
+    return span.end(rc);
 }
 
 // Greedy clue removal (sdk_minimize_batch; minimize_kernel.h): the inputs' verdicts, then 81 rounds
@@ -1993,6 +2066,47 @@ int sdk_classify_batch(sdk_ctx* c, const uint8_t* in, uint8_t* out, int8_t* stat
     int8_t* d_status = static_cast<int8_t*>(c->status.p);
     Staging io(c, {{n * 81, in, d_in, d_out, out}, {n, nullptr, nullptr, d_status, status}});
     if ((rc = io.send()) || (rc = launch_classify(c, d_in, d_out, d_status, n, budget_arg(node_budget)))) return rc;
+    return io.fetch();
+}
+
+int sdk_grade_batch_dev(sdk_ctx* c, const void* d_in, void* d_out, void* d_status, void* d_level, void* d_open,
+                        size_t n, uint64_t node_budget) {
+    if (!c || (n && (!d_in || !d_out || !d_status || !d_level))) return fail(SDK_EINVAL, "NULL argument");
+    int rc;
+    if ((rc = check_budget_arg(node_budget))) return rc;
+    if (n == 0) return SDK_OK;
+    if ((rc = check_board_count(n))) return rc;
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCALL(hipSetDevice(c->device));
+    return launch_grade(c, static_cast<const uint8_t*>(d_in), static_cast<uint8_t*>(d_out),
+                        static_cast<int8_t*>(d_status), static_cast<uint8_t*>(d_level), static_cast<uint8_t*>(d_open),
+                        n, budget_arg(node_budget));
+}
+
+int sdk_grade_batch(sdk_ctx* c, const uint8_t* in, uint8_t* out, int8_t* status, uint8_t* level, uint8_t* open,
+                    size_t n, uint64_t node_budget) {
+    if (!c || (n && (!in || !out || !status || !level))) return fail(SDK_EINVAL, "NULL argument");
+    int rc;
+    if ((rc = check_budget_arg(node_budget))) return rc;
+    if (n == 0) return SDK_OK;
+    if ((rc = check_board_count(n))) return rc;
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCALL(hipSetDevice(c->device));
+    if ((rc = ensure(c->in, n * 81)) || (rc = ensure(c->out, n * 81)) || (rc = ensure(c->status, n)) ||
+        (rc = ensure(c->gr_level, n)) || (open && (rc = ensure(c->gr_open, n))))
+        return rc;
+    uint8_t* d_in = static_cast<uint8_t*>(c->in.p);
+    uint8_t* d_out = static_cast<uint8_t*>(c->out.p);
+    int8_t* d_status = static_cast<int8_t*>(c->status.p);
+    uint8_t* d_level = static_cast<uint8_t*>(c->gr_level.p);
+    uint8_t* d_open = open ? static_cast<uint8_t*>(c->gr_open.p) : nullptr;
+    Staging io(c, {{n * 81, in, d_in, d_out, out},
+                   {n, nullptr, nullptr, d_status, status},
+                   {n, nullptr, nullptr, d_level, level},
+                   {open ? n : 0, nullptr, nullptr, d_open, open}});
+    if ((rc = io.send()) ||
+        (rc = launch_grade(c, d_in, d_out, d_status, d_level, d_open, n, budget_arg(node_budget))))
+        return rc;
     return io.fetch();
 }
 

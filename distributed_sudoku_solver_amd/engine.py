@@ -303,6 +303,26 @@ class SudokuEngine:
                 "sdk_classify_batch")
         return status, out
 
+    def grade_batch(self, boards, budget=None):
+        """uint8[n,81] -> (status int8[n], level uint8[n], open uint8[n], out uint8[n,81]): which
+        technique does each board need (sdk_grade_batch)?  status and out are classify_batch's.
+        level is 1 (naked singles), 2 (+ hidden singles), 3 (+ locked candidates) or 4 (a search)
+        for a board with exactly one completion and clean givens, 0 for every other; open is the
+        number of cells the three techniques leave open on a level-4 board, else 0.  budget as in
+        classify_batch: it bounds the search only (a board that runs out has level 0)."""
+        boards = np.ascontiguousarray(boards, dtype=np.uint8).reshape(-1, 81)
+        n = boards.shape[0]
+        if budget is not None and not 0 <= int(budget) < (1 << 63):
+            raise ValueError("budget must be 0 (unlimited) or a positive node count")
+        out = np.empty_like(boards)
+        status = np.empty(n, dtype=np.int8)
+        level = np.empty(n, dtype=np.uint8)
+        open_ = np.empty(n, dtype=np.uint8)
+        L.check(self.lib.sdk_grade_batch(self.ctx, _ptr(boards), _ptr(out), _ptr(status), _ptr(level), _ptr(open_), n,
+                                         L.SDK_BUDGET_CONTEXT if budget is None else int(budget)),
+                "sdk_grade_batch")
+        return status, level, open_, out
+
     @staticmethod
     def check_order(order, n):
         """order -> uint8[n,81], every row a permutation of 0..80 (else ValueError)."""
@@ -542,6 +562,13 @@ class SudokuEngine:
         L.check(self.lib.sdk_classify_batch_dev(self.ctx, d_in.ptr, d_out.ptr, d_status.ptr, int(n),
                                                 L.SDK_BUDGET_CONTEXT if budget is None else int(budget)),
                 "sdk_classify_batch_dev")
+
+    def grade_batch_dev(self, d_in, d_out, d_status, d_level, n, d_open=None, budget=None):
+        """d_in and d_out 16-byte aligned (d_out may be d_in); d_open optional."""
+        L.check(self.lib.sdk_grade_batch_dev(self.ctx, d_in.ptr, d_out.ptr, d_status.ptr, d_level.ptr,
+                                             d_open.ptr if d_open else None, int(n),
+                                             L.SDK_BUDGET_CONTEXT if budget is None else int(budget)),
+                "sdk_grade_batch_dev")
 
     def minimize_batch_dev(self, d_in, d_order, d_out, d_status, n):
         """The order rows are not validated on this path (see include/sudoku_hip.h)."""

@@ -45,6 +45,7 @@ extern "C" {
 #define SDK_ABI_VERSION 2   /* 2: sdk_solve_batch_ex, frontier records, p2p send/recv; version 2 */
                             /* also gained sdk_classify_batch[_dev] and sdk_minimize_batch[_dev]  */
                             /* and sdk_generate_grids[_dev] / sdk_generate_puzzles[_dev]          */
+                            /* and sdk_grade_batch[_dev]                                          */
                             /* (new symbols only: nothing a version-2 caller uses changed)        */
 
 /* return codes */
@@ -234,6 +235,45 @@ int sdk_solve_batch_ex(sdk_ctx *ctx, const uint8_t *in, const uint16_t *first_ce
  * above 2^24 boards run in slices of that many). */
 int sdk_classify_batch(sdk_ctx *ctx, const uint8_t *in, uint8_t *out, int8_t *status, size_t n,
                        uint64_t node_budget);
+
+/* Difficulty grades for n boards: which solving technique does board i need?
+ *
+ * A board's candidate state is 81 sets: a given d in 1..9 is {d}, an empty cell {1..9}; a cell is
+ * closed when exactly one candidate is left.  Three rules:
+ *   N  naked singles      an open cell loses every digit that is the candidate of a closed cell
+ *                         in one of its three units;
+ *   H  hidden singles     an open cell keeps only the candidates that some unit of its holds in
+ *                         no other cell, if it has any (two such candidates are both kept);
+ *   L  locked candidates  pointing and claiming over the 54 box-line triads: a digit that a box
+ *                         holds only in one line goes from the rest of the line, one that a line
+ *                         holds only in one box goes from the rest of the box.
+ * R1 = {N}, R2 = {N, H}, R3 = {N, H, L}; F_k(board) is the state in which no rule of R_k changes
+ * anything.  The rules only remove candidates, never a digit of a completion, and a rule that can
+ * fire stays able to fire (or becomes moot) after further removals, so F_k does not depend on the
+ * order of application: the grade is a pure function of the board.
+ *
+ *   status  sdk_classify_batch's verdict: SDK_UNSOLVABLE, SDK_SOLVED, SDK_MULTIPLE or
+ *           SDK_BUDGET_HIT; node_budget as there (SDK_BUDGET_CONTEXT = the context's).  The
+ *           propagation steps are free: a budget only bounds the search of the boards they leave.
+ *   out     as classify: the completion for SDK_SOLVED, else the input.
+ *   level   uint8[n].  For a board with status SDK_SOLVED and clean givens (all in 0..9, none
+ *           repeated in a unit): the smallest k in 1..3 for which every cell of F_k is closed
+ *           (SDK_GRADE_NAKED / _HIDDEN / _LOCKED), or SDK_GRADE_SEARCH if there is none.
+ *           SDK_GRADE_NONE for every other board -- a uniquely solvable board with an inert
+ *           (10..255) or duplicated given included.
+ *   open    uint8[n], nullable.  For a board of level SDK_GRADE_SEARCH the number of open cells of
+ *           F_3 (what the techniques left to the search); 0 for every other board.
+ * The search's node count is deliberately not part of the grade: it depends on the boards a
+ * board shares a wave with.  The grading pass always runs, for any n, whatever SDK_OPT_PROP32*,
+ * SDK_OPT_SOLVER, SDK_OPT_ORDER and SDK_OPT_DONATE say; the call changes no option.  Any n up to
+ * 2^31-1 (slices of 2^24 boards); one span under SDK_OPT_TIMING. */
+#define SDK_GRADE_NONE   0
+#define SDK_GRADE_NAKED  1
+#define SDK_GRADE_HIDDEN 2
+#define SDK_GRADE_LOCKED 3
+#define SDK_GRADE_SEARCH 4
+int sdk_grade_batch(sdk_ctx *ctx, const uint8_t *in, uint8_t *out, int8_t *status, uint8_t *level,
+                    uint8_t *open, size_t n, uint64_t node_budget);
 
 /* Greedy clue removal for n boards.  order is uint8[n][81]; row i is a permutation of 0..80, the
  * cell order in which board i's clues are tried (anything else: SDK_EINVAL).  Per board:
@@ -427,6 +467,10 @@ int sdk_classify_batch_dev(sdk_ctx *ctx, const void *d_in, void *d_out, void *d_
  * repeated cell is tried again (a no-op: it is empty, or it could not go). */
 int sdk_minimize_batch_dev(sdk_ctx *ctx, const void *d_in, const void *d_order, void *d_out,
                            void *d_status, size_t n);
+/* d_in and d_out 16-byte aligned, else SDK_EINVAL (this form never skips the pass); d_out may be
+ * d_in (exactly: any other overlap is undefined).  d_level uint8[n], d_open uint8[n] or NULL. */
+int sdk_grade_batch_dev(sdk_ctx *ctx, const void *d_in, void *d_out, void *d_status, void *d_level,
+                        void *d_open, size_t n, uint64_t node_budget);
 /* d_grids (and d_order, d_puzzles) 16-byte aligned, else SDK_EINVAL; d_order and d_placements
  * (uint32[n]) nullable.  Spans as the host-pointer forms: one per call. */
 int sdk_generate_grids_dev(sdk_ctx *ctx, uint64_t seed, uint64_t first, size_t n, void *d_grids,
