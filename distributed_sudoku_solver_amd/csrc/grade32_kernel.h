@@ -1,8 +1,9 @@
 // grade32_kernel.h -- the propagation pass run as a grader: which technique does a board need?
 // (sdk_grade_batch; include/sudoku_hip.h has the contract, DESIGN.md "Grading" the measurements)
 //
-// Same layout and the same device functions as prop32_kernel.h: bit b of a word is board b of the
-// half's 32, lane hl < 27 owns row triad hl and unit hl.  What differs is the schedule.  The fast pass
+// Same layout, the same device functions and the same group driver as prop32_kernel.h (p32_group_begin,
+// p32_run, p32_decide, p32_refute_handed, p32_group_end): bit b of a word is board b of the half's 32,
+// lane hl < 27 owns row triad hl and unit hl.  Only the schedule of a step is this file's.  The fast pass
 // runs naked singles (N), hidden singles (H) and locked candidates (L) together, on a schedule tuned
 // for speed; here every board climbs R1 = {N}, R2 = {N, H}, R3 = {N, H, L} one set at a time and only
 // from a fixpoint of the set it is in, so the set it holds when it is found solved is its level.
@@ -38,7 +39,7 @@
 // bit extracts per group that has a stuck board, against ~120 LDS instructions per step: cheaper
 // than a bit-sliced adder tree across lanes (seven planes through five DPP stages), and no state.
 //
-// Outputs.  status / out / the undecided list exactly as prop32_kernel (handover, the "digit closed
+// Outputs.  status / out / the undecided list are the shared driver's (handover, the "digit closed
 // twice" refutation of a handed grid included); level[] for every board: 1..3 solved, 4 stuck
 // (provisional: g32_verdict_kernel clears it unless the search finds exactly one completion), 0
 // refuted or inexact; open[] the count for stuck boards, else 0.
@@ -90,32 +91,15 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) void gr
     const Prop32Args& a = ga.p;
     __shared__ __attribute__((aligned(16))) uint8_t s_lds[kP32Lds];
     p32_lds_t* const lds = (p32_lds_t*)s_lds;
-    p32_order_table(lds);
-    __builtin_amdgcn_wave_barrier();
-    P32Lane w;
-    w.half = threadIdx.x >> 5;
-    w.hl = threadIdx.x & 31;
-    w.act = w.hl < 27;
-    w.reg = lds + w.half * kP32Region;
+    const P32Lane w = p32_wave_begin(lds);
     const uint32_t groups = (uint32_t)((a.n + 63) / 64);
     uint32_t seg = blockIdx.x % kP32Heads;
     for (;;) {
         const uint32_t g = p32_dequeue(a, groups, seg);
         if (g == ~0u) break;
-        const uint64_t base = (uint64_t)g * 64;
-        const uint32_t nb = (uint32_t)min<uint64_t>(64, a.n - base);
-        const uint8_t* src = a.in + base * 81;
         P32Cells x;
-        uint64_t inert64;
-        {
-            uint32_t d[32];
-            p32_load(src, nb, d);
-            const uint32_t hi = p32_convert(d, x);
-            inert64 = p32_mask64(p32_half_or(w.act ? hi : 0u));
-        }
-        const uint64_t valid = nb >= 64u ? ~0ull : ((1ull << nb) - 1ull);
-        uint64_t undec = inert64 & valid, inexact = undec;
-        uint64_t live = valid & ~undec, solved = 0ull, contra = 0ull;
+        P32Group G;
+        p32_group_begin(a, w, g, x, G);
         uint64_t hid = 0ull, lck = 0ull;   // the boards' technique masks
         uint64_t fixl = 0ull;              // lck boards unchanged by the step before this locked pass
         bool lc = false;
@@ -123,9 +107,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) void gr
 #if SDK_GRADE32_STATS
         uint32_t st_lc = 0;
 #endif
-        // one step; as in prop32_body every path through it ends in an update of the cell words, and
-        // the loop runs two per iteration
-        auto step = [&]() {
+        p32_run(G, [&]() {
             uint32_t empty, alls;
             p32_singles(w, x, empty, alls);
             __builtin_amdgcn_wave_barrier();
@@ -138,49 +120,29 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) void gr
                 for (int k = 0; k < 3; ++k) x.s[k] |= off;
                 const uint32_t lc_own = p32_locked(w, x);
                 const uint64_t lchg = p32_mask64(p32_half_or(w.act ? lc_own : 0u));
-                const uint64_t stuck = fixl & ~lchg & live;
-                undec |= stuck;
-                live &= ~stuck;
+                const uint64_t stuck = fixl & ~lchg & G.live;
+                G.undec |= stuck;
+                G.live &= ~stuck;
                 fixl = 0ull;
                 lc = false;
                 __builtin_amdgcn_wave_barrier();
                 return;
             }
-            uint32_t miss, dup = 0u;
-            if (it == 0) {   // a digit given twice: not exact, to the search
-                p32_unit<true>(w, lds, miss, dup);
-                const uint64_t dupw = p32_mask64(p32_half_or(w.act ? dup : 0u)) & live;
-                undec |= dupw;
-                inexact |= dupw;
-                live &= ~dupw;
-            } else {
-                p32_unit<false>(w, lds, miss, dup);
-            }
-            const uint64_t badw = p32_mask64(p32_half_or(w.act ? (miss | empty) : 0u));
-            const uint64_t allw = p32_mask64(p32_half_and(w.act ? alls : ~0u));
-            const uint64_t sv = allw & ~badw & live, ct = badw & live;
-            solved |= sv;
-            contra |= ct;
-            live &= ~(sv | ct);
-            if (live != 0ull && ++it >= kG32MaxSteps) {   // (unreachable: see the header)
-                undec |= live;
-                live = 0ull;
+            p32_decide(w, lds, it == 0, empty, alls, G);
+            if (G.live != 0ull && ++it >= kG32MaxSteps) {   // (unreachable: see the header)
+                G.undec |= G.live;
+                G.live = 0ull;
             }
             __builtin_amdgcn_wave_barrier();
             const uint32_t chg_own = p32_cells<true, true>(w, x, g32_word(w, hid));
-            const uint64_t unch = live & ~p32_mask64(p32_half_or(w.act ? chg_own : 0u));
+            const uint64_t unch = G.live & ~p32_mask64(p32_half_or(w.act ? chg_own : 0u));
             // at a fixpoint of its set: the next set, or the locked pass that tells whether it is F_3
             fixl = unch & hid;
             lck |= fixl;
             hid |= unch;
             lc = fixl != 0ull;
             __builtin_amdgcn_wave_barrier();
-        };
-        while (live != 0ull) {
-            step();
-            if (live == 0ull) break;
-            step();
-        }
+        });
 #if SDK_GRADE32_STATS
         if (threadIdx.x == 0) {
             G32_STAT(0, it);
@@ -189,21 +151,14 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) void gr
 #endif
         __builtin_amdgcn_wave_barrier();
         // the stuck boards (undecided, exact): their open cells, and with handover their grids
-        uint64_t stuck = undec & ~inexact;
+        uint64_t stuck = G.undec & ~G.inexact;
         uint64_t handed = a.handover ? stuck : 0ull;
         uint32_t nopen = 0u;
         if (stuck) {
             uint32_t empty, alls;
-            p32_singles(w, x, empty, alls);
+            p32_singles(w, x, empty, alls);   // for the refutation and for the count
             __builtin_amdgcn_wave_barrier();
-            if (handed) {
-                // two closed cells with one digit in a unit: no completion (prop32_body)
-                const uint64_t dupw = p32_mask64(p32_half_or(w.act ? p32_dups(w, lds) : 0u)) & handed;
-                contra |= dupw;
-                undec &= ~dupw;
-                handed &= ~dupw;
-                stuck &= ~dupw;
-            }
+            if (handed) stuck &= ~p32_refute_handed(w, lds, G, handed);
             // this lane as board (half, hl): the clear bits hl of its half's 81 single words
             const uint32_t bit = p32_opq(w.hl);
 #pragma unroll 9
@@ -214,18 +169,15 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) void gr
             }
             __builtin_amdgcn_wave_barrier();
         }
-        p32_answers(a, w, x, lds, base, nb, solved, contra, handed);
-        // statuses and grades; the undecided boards are listed for the search
+        // the grades; then the answers, the statuses and the list
         const uint32_t me = p32_opq(threadIdx.x);        // board me of the group (32 half + hl)
-        if ((valid >> me) & 1ull) {
-            const bool sv = (solved >> me) & 1ull, st = (stuck >> me) & 1ull;
-            a.status[base + me] = (int8_t)(sv ? 1 : (((contra >> me) & 1ull) ? 0 : kStUndecided));
-            ga.level[base + me] =
+        if ((G.valid >> me) & 1ull) {
+            const bool sv = (G.solved >> me) & 1ull, st = (stuck >> me) & 1ull;
+            ga.level[G.base + me] =
                 (uint8_t)(sv ? 1u + (uint32_t)((hid >> me) & 1ull) + (uint32_t)((lck >> me) & 1ull) : (st ? 4u : 0u));
-            ga.open[base + me] = (uint8_t)(st ? nopen : 0u);
+            ga.open[G.base + me] = (uint8_t)(st ? nopen : 0u);
         }
-        p32_list_undecided(a, lds, base, me, undec, handed);
-        __builtin_amdgcn_wave_barrier();
+        p32_group_end(a, w, x, lds, G, handed);
     }
 }
 #endif

@@ -88,21 +88,13 @@ struct Prop32Args {
 // odd rows of one register trade places with the even rows of another; on two copies of x the OR
 // of both is row 0 | row 1 in each half), a VALU op, where the ds_swizzle it replaces (lane ^ 16)
 // went through the LDS pipe that bounds the kernel.  Every lane of the wave must be active.
-#ifndef SDK_PROP32_PERMLANE
-#define SDK_PROP32_PERMLANE 1
-#endif
 __device__ __forceinline__ uint32_t p32_half_or(uint32_t x) {
     x |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x121, 0xF, 0xF, false);   // row_ror:1
     x |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x122, 0xF, 0xF, false);   // row_ror:2
     x |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x124, 0xF, 0xF, false);   // row_ror:4
     x |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x128, 0xF, 0xF, false);   // row_ror:8
-#if SDK_PROP32_PERMLANE
     const auto r = __builtin_amdgcn_permlane16_swap(x, x, false, false);
     return r[0] | r[1];
-#else
-    x |= (uint32_t)__builtin_amdgcn_ds_swizzle((int)x, 0x401F);
-    return x;
-#endif
 }
 __device__ __forceinline__ uint32_t p32_half_and(uint32_t x) { return ~p32_half_or(~x); }
 
@@ -132,13 +124,10 @@ __device__ __forceinline__ uint2 p32_lda(uint32_t addr) {   // an absolute LDS a
     return make_uint2((uint32_t)v, (uint32_t)(v >> 32));
 }
 // stores volatile too: merged pairs become ds_write2_b64, 13 cycles against 2 x 6 (same table)
-// The unit phase's per-lane read-order table (p32_order_table): SDK_PROP32_TABLE16 keeps the nine
-// record addresses as 16-bit halves (three ds_read_b64 per step, halves split by VOP2 shifts and
-// masks) instead of 32-bit words (five reads) -- two LDS instructions fewer per step on the pipe
-// that bounds the kernel, for nine pairing VALU ops
-#ifndef SDK_PROP32_TABLE16
-#define SDK_PROP32_TABLE16 1
-#endif
+// The unit phase's per-lane read-order table (p32_order_table) keeps the nine record addresses as
+// 16-bit halves (three ds_read_b64 per step, halves split by VOP2 shifts and masks) instead of
+// 32-bit words (five reads) -- two LDS instructions fewer per step on the pipe that bounds the
+// kernel, for nine pairing VALU ops
 __device__ __forceinline__ uint64_t p32_tab64(const p32_lds_t* lds, uint32_t off) {
     return *(const volatile __attribute__((address_space(3))) uint64_t*)(lds + off);
 }
@@ -296,17 +285,11 @@ __device__ __forceinline__ uint32_t p32_dups(const P32Lane& w, const p32_lds_t* 
     // the unit's cells from p32_unit's order table (any order will do; no lane-dependent branch)
     const uint32_t tb = kP32Table + 40u * p32_opq(threadIdx.x);
     uint32_t T[9], dup = 0u;
-#if SDK_PROP32_TABLE16
     uint64_t tw = 0ull;
-#endif
 #pragma unroll
     for (int q = 0; q < 9; ++q) {
-#if SDK_PROP32_TABLE16
         if (q % 4 == 0) tw = p32_tab64(lds, tb + 2u * q);
         const uint32_t o = p32_tab_field(tw, q % 4);
-#else
-        const uint32_t o = *(const volatile __attribute__((address_space(3))) uint32_t*)(lds + tb + 4u * (q < 3 ? q : q + 1));
-#endif
         const uint2 r0 = p32_lda(o), r1 = p32_lda(o + 8), r2 = p32_lda(o + 16), r3 = p32_lda(o + 24),
                     r4 = p32_lda(o + 32);
         const uint32_t a[9] = {r0.x, r0.y, r1.x, r1.y, r2.x, r2.y, r3.x, r3.y, r4.x};
@@ -336,7 +319,7 @@ __device__ __forceinline__ uint32_t p32_dups(const P32Lane& w, const p32_lds_t* 
 // so that those nine cells' records (40 B apart) fall in nine different bank pairs (cell index mod 32
 // distinct in every digit class; found by a search over relabelled and permuted pattern grids).  The
 // natural order met two addresses per bank pair on every read (15-16 % of the launch's LDS cycles
-// were bank conflicts).  The per-lane offsets are a table in LDS (40 B per lane; SDK_PROP32_TABLE16 above).
+// were bank conflicts).  The per-lane offsets are a table in LDS (40 B per lane; 16-bit entries, above).
 // kDups (a group's first step): also the digits given twice in the unit (p32_dups) from the same
 // loaded records -- a digit closed in at least two of the unit's cells: the majority of three closed
 // terms over the first three cells, then of (closed so far, the pair's two closed terms) -- instead of
@@ -346,25 +329,14 @@ __device__ __forceinline__ void p32_unit(const P32Lane& w, const p32_lds_t* lds,
     const uint32_t j = p32_opq(w.hl);   // the unit record written below
     const uint32_t tb = kP32Table + 40u * p32_opq(threadIdx.x);
     uint32_t ones[9], twos[9], T[9];
-#if SDK_PROP32_TABLE16
     uint64_t tA, tB = 0ull;   // table words: steps 0-3, 4-7 (step 8: its own read)
-#endif
     // cells 0, 1, 2
     {
         uint32_t a[3][9], s[3];
-#if SDK_PROP32_TABLE16
         tA = p32_tab64(lds, tb);
-#else
-        const uint64_t o01 = *(const volatile __attribute__((address_space(3))) uint64_t*)(lds + tb);
-        const uint32_t o2 = *(const volatile __attribute__((address_space(3))) uint32_t*)(lds + tb + 8u);
-#endif
 #pragma unroll
         for (int q = 0; q < 3; ++q) {
-#if SDK_PROP32_TABLE16
             const uint32_t o = p32_tab_field(tA, q);
-#else
-            const uint32_t o = q == 0 ? (uint32_t)o01 : q == 1 ? (uint32_t)(o01 >> 32) : o2;
-#endif
             const uint2 r0 = p32_lda(o), r1 = p32_lda(o + 8), r2 = p32_lda(o + 16), r3 = p32_lda(o + 24),
                         r4 = p32_lda(o + 32);
             a[q][0] = r0.x; a[q][1] = r0.y; a[q][2] = r1.x; a[q][3] = r1.y; a[q][4] = r2.x;
@@ -388,7 +360,6 @@ __device__ __forceinline__ void p32_unit(const P32Lane& w, const p32_lds_t* lds,
                      "+v"(T[0]), "+v"(T[1]), "+v"(T[2]), "+v"(T[3]), "+v"(T[4]), "+v"(T[5]), "+v"(T[6]),
                      "+v"(T[7]), "+v"(T[8])::"memory");
         uint32_t a[2][9], s[2];
-#if SDK_PROP32_TABLE16
         // steps 3 + 2p, 4 + 2p: (3, 4) from words A and B, (5, 6) from B, (7, 8) from B and C
         uint32_t oo[2];
         if (p == 0) {
@@ -402,16 +373,9 @@ __device__ __forceinline__ void p32_unit(const P32Lane& w, const p32_lds_t* lds,
             oo[0] = p32_tab_field(tB, 3);
             oo[1] = p32_tab_field(p32_tab64(lds, tb + 16u), 0);
         }
-#else
-        const uint64_t op = *(const volatile __attribute__((address_space(3))) uint64_t*)(lds + tb + 16u + 8u * p);
-#endif
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
-#if SDK_PROP32_TABLE16
             const uint32_t o = oo[h];
-#else
-            const uint32_t o = h == 0 ? (uint32_t)op : (uint32_t)(op >> 32);
-#endif
             const uint2 r0 = p32_lda(o), r1 = p32_lda(o + 8), r2 = p32_lda(o + 16), r3 = p32_lda(o + 24),
                         r4 = p32_lda(o + 32);
             a[h][0] = r0.x; a[h][1] = r0.y; a[h][2] = r1.x; a[h][3] = r1.y; a[h][4] = r2.x;
@@ -817,6 +781,108 @@ __device__ __forceinline__ void p32_list_undecided(const Prop32Args& a, const p3
     }
 }
 
+// The group driver both kernels run their schedules in (prop32_body; the grading pass,
+// grade32_kernel.h): p32_group_begin, p32_run over the kernel's own step -- which calls p32_decide --
+// then p32_refute_handed for the handed-over boards and p32_group_end.
+//
+// A group's bookkeeping: 64-bit board masks in scalar registers (bit 32h + b: board b of half h).
+struct P32Group {
+    uint64_t base;       // the group's first board
+    uint32_t nb;         // its boards (64, fewer in the batch's last group)
+    uint64_t valid;      // the nb boards
+    uint64_t undec;      // left to the search (listed)
+    uint64_t inexact;    // ... of them, those with an inert or duplicated given: never handed over
+    uint64_t live;       // still propagating
+    uint64_t solved, contra;
+};
+
+// Group g's boards into registers and on to the bit-sliced candidate words: digit v -> one word,
+// 0 -> all nine; the boards with a given > 9 (inert cells, undecided here; their words do not matter)
+// from the same planes.
+__device__ __forceinline__ void p32_group_begin(const Prop32Args& a, const P32Lane& w, uint32_t g, P32Cells& x,
+                                                P32Group& G) {
+    G.base = (uint64_t)g * 64;
+    G.nb = (uint32_t)min<uint64_t>(64, a.n - G.base);
+    uint64_t inert64;
+    {
+        uint32_t d[32];
+        p32_load(a.in + G.base * 81, G.nb, d);
+        const uint32_t hi = p32_convert(d, x);
+        inert64 = p32_mask64(p32_half_or(w.act ? hi : 0u));
+    }
+    G.valid = G.nb >= 64u ? ~0ull : ((1ull << G.nb) - 1ull);
+    G.undec = inert64 & G.valid;
+    G.inexact = G.undec;
+    G.live = G.valid & ~G.undec;
+    G.solved = 0ull;
+    G.contra = 0ull;
+}
+
+// The group's steps.  One exit, at the head: a group that ends in a step still runs that step's cells
+// phase (sound propagation; it only tightens what a handed-over board carries), so every path through
+// a step ends in an update of the cell words and they keep one register home (with exits in the middle
+// of the step the register allocator gave the words a second home and copied all 27 out and back on
+// every step).  Two steps per iteration, so the two copies' register homes of the cell words can
+// alternate instead of being copied back at every latch.
+template <class Step>
+__device__ __forceinline__ void p32_run(const P32Group& G, Step&& step) {
+    while (G.live != 0ull) {
+        step();
+        if (G.live == 0ull) break;
+        step();
+    }
+}
+
+// The unit phase of a step (the cell records of p32_singles are in LDS; empty, alls: its results) and
+// what it decides: a board with every cell closed and no unit missing a digit is solved, one with an
+// empty cell or a missing digit has no completion.  first (a group's first step, the closed cells
+// are the givens): a board with a digit given twice is not exact, and goes to the search.
+__device__ __forceinline__ void p32_decide(const P32Lane& w, const p32_lds_t* lds, bool first, uint32_t empty,
+                                           uint32_t alls, P32Group& G) {
+    uint32_t miss, dup = 0u;
+    if (first) {
+        p32_unit<true>(w, lds, miss, dup);
+        const uint64_t dupw = p32_mask64(p32_half_or(w.act ? dup : 0u)) & G.live;
+        G.undec |= dupw;
+        G.inexact |= dupw;
+        G.live &= ~dupw;
+    } else {
+        p32_unit<false>(w, lds, miss, dup);
+    }
+    const uint64_t badw = p32_mask64(p32_half_or(w.act ? (miss | empty) : 0u));
+    const uint64_t allw = p32_mask64(p32_half_and(w.act ? alls : ~0u));
+    const uint64_t sv = allw & ~badw & G.live, ct = badw & G.live;
+    G.solved |= sv;
+    G.contra |= ct;
+    G.live &= ~(sv | ct);
+}
+
+// After the steps, for the boards about to be handed over (the cell records of a p32_singles over the
+// final state are in LDS): a handed-over grid is searched as a board of its own, where two closed
+// cells with one digit in a unit would be duplicated givens (whose reference semantics differ); here
+// they are a contradiction -- such a board has no completion.  Returns the boards refuted.
+__device__ __forceinline__ uint64_t p32_refute_handed(const P32Lane& w, const p32_lds_t* lds, P32Group& G,
+                                                      uint64_t& handed) {
+    const uint64_t dupw = p32_mask64(p32_half_or(w.act ? p32_dups(w, lds) : 0u)) & handed;
+    G.contra |= dupw;
+    G.undec &= ~dupw;
+    handed &= ~dupw;
+    return dupw;
+}
+
+// The group's results: the answers through the staging, the statuses, and the undecided boards onto
+// the list for the search (both read the staging), and the group's closing barrier.
+__device__ __forceinline__ void p32_group_end(const Prop32Args& a, const P32Lane& w, const P32Cells& x,
+                                              p32_lds_t* lds, const P32Group& G, uint64_t handed) {
+    p32_answers(a, w, x, lds, G.base, G.nb, G.solved, G.contra, handed);
+    const uint32_t me = p32_opq(threadIdx.x);        // board me of the group (32 half + hl)
+    if ((G.valid >> me) & 1ull)
+        a.status[G.base + me] =
+            (int8_t)(((G.solved >> me) & 1ull) ? 1 : (((G.contra >> me) & 1ull) ? 0 : kStUndecided));
+    p32_list_undecided(a, lds, G.base, me, G.undec, handed);
+    __builtin_amdgcn_wave_barrier();
+}
+
 // SDK_PROP32_STATS (profiling builds only): per group, histograms of the steps it ran, of the step at
 // which at most 4 / at most 1 of its boards were still live, and the locked-candidates passes
 #ifndef SDK_PROP32_STATS
@@ -869,27 +935,35 @@ static __constant__ uint8_t kP32Order[81] = {2, 5, 8, 1, 4, 7, 3, 0, 6, 1, 4, 7,
                                       2, 7, 4, 1, 5, 8, 2, 4, 7, 1, 6, 3, 0, 4, 7, 1, 3, 6, 0, 5, 2, 8, 3, 6, 0,
                                       2, 5, 8, 4, 1, 7};
 
-// p32_unit's per-lane read order, lane L (half L / 32, unit L % 32) at kP32Table + 40 L: word t = the
-// LDS address of the cell of the unit whose kP32Order entry is t, in the lane's half (no per-read
-// address add).  Spare lanes take unit 0's (one more reader of each address).  Written once per
-// workgroup.
+// p32_unit's per-lane read order, lane L (half L / 32, unit L % 32) at kP32Table + 40 L: 16-bit entry
+// t = the LDS address of the cell of the unit whose kP32Order entry is t, in the lane's half (no
+// per-read address add).  Spare lanes take unit 0's (one more reader of each address).  Written once
+// per workgroup.
 __device__ __forceinline__ void p32_order_table(p32_lds_t* lds) {
     const uint32_t hl = threadIdx.x & 31u;
     uint32_t u0, ua, ub;
     p32_unit_cells(hl < 27 ? hl : 0u, u0, ua, ub);
-    __attribute__((address_space(3))) uint32_t* tab =
-        (__attribute__((address_space(3))) uint32_t*)(lds + kP32Table + 40u * threadIdx.x);
+    __attribute__((address_space(3))) uint16_t* tab =
+        (__attribute__((address_space(3))) uint16_t*)(lds + kP32Table + 40u * threadIdx.x);
     const uint32_t region = (uint32_t)(uintptr_t)lds + (threadIdx.x >> 5) * kP32Region;
     for (uint32_t q = 0; q < 9; ++q) {
         const uint32_t o = u0 + (q % 3) * ua + (q / 3) * ub;
         const uint32_t t = kP32Order[o / kP32Rec];
-#if SDK_PROP32_TABLE16
         static_assert(kP32Lds <= 65536u, "16-bit table entries");
-        ((__attribute__((address_space(3))) uint16_t*)tab)[t] = (uint16_t)(region + o);   // halves 0-8
-#else
-        tab[t < 3u ? t : t + 1u] = region + o;   // words 0-2, then the pairs (3, 4) .. (7, 8) 8-byte aligned
-#endif
+        tab[t] = (uint16_t)(region + o);
     }
+}
+
+// A wave's set-up, once per workgroup: the order table, and the lane's place in its half.
+__device__ __forceinline__ P32Lane p32_wave_begin(p32_lds_t* lds) {
+    p32_order_table(lds);
+    __builtin_amdgcn_wave_barrier();
+    P32Lane w;
+    w.half = threadIdx.x >> 5;
+    w.hl = threadIdx.x & 31;
+    w.act = w.hl < 27;
+    w.reg = lds + w.half * kP32Region;
+    return w;
 }
 
 #endif
@@ -911,51 +985,23 @@ __device__ __forceinline__ void prop32_body(Prop32Args a, uint64_t* stamps) {
         o[0] = __builtin_amdgcn_s_memtime();
         o[1] = __builtin_amdgcn_s_memrealtime();
     }
-    p32_order_table(lds);
-    __builtin_amdgcn_wave_barrier();
-    P32Lane w;
-    w.half = threadIdx.x >> 5;
-    w.hl = threadIdx.x & 31;
-    w.act = w.hl < 27;
-    w.reg = lds + w.half * kP32Region;
+    const P32Lane w = p32_wave_begin(lds);
     const uint32_t groups = (uint32_t)((a.n + 63) / 64);
     uint32_t seg = blockIdx.x % kP32Heads;
     for (;;) {
         const uint32_t g = p32_dequeue(a, groups, seg);
         if (g == ~0u) break;
-        const uint64_t base = (uint64_t)g * 64;
-        const uint32_t nb = (uint32_t)min<uint64_t>(64, a.n - base);
-        const uint8_t* src = a.in + base * 81;
-        // the group's boards into registers and on to the bit-sliced candidate words: digit v -> one
-        // word, 0 -> all nine; the boards with a given > 9 (inert cells, undecided here; their words do
-        // not matter) from the same planes
         P32Cells x;
-        uint64_t inert64;
-        {
-            uint32_t d[32];
-            p32_load(src, nb, d);
-            const uint32_t hi = p32_convert(d, x);
-            inert64 = p32_mask64(p32_half_or(w.act ? hi : 0u));
-        }
-        // per-group bookkeeping as 64-bit board masks in scalar registers (bit 32h + b: board b of
-        // half h)
-        const uint64_t valid = nb >= 64u ? ~0ull : ((1ull << nb) - 1ull);
-        uint64_t undec = inert64 & valid, inexact = undec;
-        uint64_t live = valid & ~undec, solved = 0ull, contra = 0ull, fixw = 0ull;
+        P32Group G;
+        p32_group_begin(a, w, g, x, G);
+        uint64_t fixw = 0ull;              // live boards unchanged by the step before this locked pass
         bool lc = false;
         uint32_t next_lc = a.lc_first;     // the step after which the next locked-candidates pass runs
 #if SDK_PROP32_STATS
         uint32_t st_lc = 0, st_t4 = ~0u, st_t1 = ~0u;
 #endif
         uint32_t it = 0;
-        // One exit, at the head: a group that ends in a step still runs that step's cells phase (sound
-        // propagation; it only tightens what a handed-over board carries), so every path through the
-        // body ends in an update of the cell words and they keep one register home (with exits in the
-        // middle of the step the register allocator gave the words a second home and copied all 27
-        // out and back on every step)
-        // one step (see above); the loop runs two per iteration, so the two copies' register homes of
-        // the cell words can alternate instead of being copied back at every latch
-        auto step = [&]() {
+        p32_run(G, [&]() {
             uint32_t empty, alls;
             p32_singles(w, x, empty, alls);
             __builtin_amdgcn_wave_barrier();
@@ -965,62 +1011,42 @@ __device__ __forceinline__ void prop32_body(Prop32Args a, uint64_t* stamps) {
 #endif
                 const uint32_t lc_own = p32_locked(w, x);
                 const uint64_t lchg = p32_mask64(p32_half_or(w.act ? lc_own : 0u));
-                const uint64_t stuck = fixw & ~lchg & live;
-                undec |= stuck;
-                live &= ~stuck;
+                const uint64_t stuck = fixw & ~lchg & G.live;
+                G.undec |= stuck;
+                G.live &= ~stuck;
                 fixw = 0ull;
                 lc = false;
                 __builtin_amdgcn_wave_barrier();
                 return;
             }
-            uint32_t miss, dup = 0u;
-            if (it == 0) {   // a digit given twice: not exact, to the search
-                p32_unit<true>(w, lds, miss, dup);
-                const uint64_t dupw = p32_mask64(p32_half_or(w.act ? dup : 0u)) & live;
-                undec |= dupw;
-                inexact |= dupw;
-                live &= ~dupw;
-            } else {
-                p32_unit<false>(w, lds, miss, dup);
-            }
-            const uint64_t badw = p32_mask64(p32_half_or(w.act ? (miss | empty) : 0u));
-            const uint64_t allw = p32_mask64(p32_half_and(w.act ? alls : ~0u));
-            const uint64_t sv = allw & ~badw & live, ct = badw & live;
-            solved |= sv;
-            contra |= ct;
-            live &= ~(sv | ct);
+            p32_decide(w, lds, it == 0, empty, alls, G);
 #if SDK_PROP32_STATS
-            if (st_t4 == ~0u && __builtin_popcountll(live) <= 4) st_t4 = it;
-            if (st_t1 == ~0u && __builtin_popcountll(live) <= 1) st_t1 = it;
+            if (st_t4 == ~0u && __builtin_popcountll(G.live) <= 4) st_t4 = it;
+            if (st_t1 == ~0u && __builtin_popcountll(G.live) <= 1) st_t1 = it;
 #endif
-            if (live != 0ull) {
-                if (a.tail_live && it >= a.tail_step && (uint32_t)__builtin_popcountll(live) <= a.tail_live) {
-                    undec |= live;   // the last few boards go to the search with their propagated grids
-                    live = 0ull;
+            if (G.live != 0ull) {
+                if (a.tail_live && it >= a.tail_step && (uint32_t)__builtin_popcountll(G.live) <= a.tail_live) {
+                    G.undec |= G.live;   // the last few boards go to the search with their propagated grids
+                    G.live = 0ull;
                 } else if (++it >= a.max_steps) {
-                    undec |= live;
-                    live = 0ull;
+                    G.undec |= G.live;
+                    G.live = 0ull;
                 }
             }
             __builtin_amdgcn_wave_barrier();
             // step lc_first and every lc_every-th after it are followed by a locked-candidates pass;
             // that step also reports which boards it left unchanged (a board unchanged by it and by
             // the pass is stuck)
-            lc = live != 0ull && it == next_lc;
+            lc = G.live != 0ull && it == next_lc;
             if (lc) next_lc += a.lc_every;
             if (lc) {
                 const uint32_t chg_own = p32_cells<true>(w, x);
-                fixw = live & ~p32_mask64(p32_half_or(w.act ? chg_own : 0u));
+                fixw = G.live & ~p32_mask64(p32_half_or(w.act ? chg_own : 0u));
             } else {
                 (void)p32_cells<false>(w, x);
             }
             __builtin_amdgcn_wave_barrier();
-        };
-        while (live != 0ull) {
-            step();
-            if (live == 0ull) break;
-            step();
-        }
+        });
 #if SDK_PROP32_STATS
         if (threadIdx.x == 0) {
             P32_STAT(0, it);
@@ -1030,29 +1056,15 @@ __device__ __forceinline__ void prop32_body(Prop32Args a, uint64_t* stamps) {
         }
 #endif
         __builtin_amdgcn_wave_barrier();
-        // the answers, in the staging: solved boards' digits (binary planes of the one-hot words),
-        // boards without a completion their input (DHT_Node.py:535); then out, for the whole group
-        uint64_t handed = a.handover ? undec & ~inexact : 0ull;   // listed with their grids
+        uint64_t handed = a.handover ? G.undec & ~G.inexact : 0ull;   // listed with their grids
         if (handed) {
-            // a handed-over grid is searched as a board of its own: two closed cells with one digit
-            // in a unit would be duplicated givens there (whose reference semantics differ), and they
-            // are a contradiction here -- such a board has no completion
             uint32_t empty, alls;
             p32_singles(w, x, empty, alls);
             __builtin_amdgcn_wave_barrier();
-            const uint64_t dupw = p32_mask64(p32_half_or(w.act ? p32_dups(w, lds) : 0u)) & handed;
-            contra |= dupw;
-            undec &= ~dupw;
-            handed &= ~dupw;
+            (void)p32_refute_handed(w, lds, G, handed);
             __builtin_amdgcn_wave_barrier();
         }
-        p32_answers(a, w, x, lds, base, nb, solved, contra, handed);
-        // statuses; the undecided boards are listed with their inputs for the search
-        const uint32_t me = p32_opq(threadIdx.x);        // board me of the group (32 half + hl)
-        if ((valid >> me) & 1ull)
-            a.status[base + me] = (int8_t)(((solved >> me) & 1ull) ? 1 : (((contra >> me) & 1ull) ? 0 : kStUndecided));
-        p32_list_undecided(a, lds, base, me, undec, handed);
-        __builtin_amdgcn_wave_barrier();
+        p32_group_end(a, w, x, lds, G, handed);
     }
     if (kStamp) {
         const uint64_t t1 = __builtin_amdgcn_s_memtime(), r1 = __builtin_amdgcn_s_memrealtime();

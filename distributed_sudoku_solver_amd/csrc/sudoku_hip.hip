@@ -961,6 +961,57 @@ int launch_solve(sdk_ctx* c, const SolveCall& call) {
     return span.end(rc);
 }
 
+// The host side the two propagation passes share (prop32_kernel; the grading pass, grade32_kernel):
+// workspaces, a pass's control words and common arguments, and the fallback over the boards it lists.
+constexpr size_t kCtlBytes = (size_t)sdk::kP32Heads * sdk::kP32HeadStride * 4;   // the dequeue counters
+
+// the pass's workspaces, for passes over at most `cap` boards
+int p32_reserve(sdk_ctx* c, size_t cap) {
+    int rc;
+    if ((rc = ensure(c->p32_ctl, kCtlBytes)) || (rc = ensure(c->p32_list, (cap + 1) * 4)) ||
+        (rc = ensure(c->p32_in, cap * 81)) || (rc = ensure(c->p32_out, cap * 81)) || (rc = ensure(c->p32_st, cap)))
+        return rc;
+    return SDK_OK;
+}
+
+// One pass over n boards: its dequeue counters and the list's length cleared (enqueued), and the
+// arguments both kernels take; budget: the resolved node budget of the search that follows.
+int p32_pass_begin(sdk_ctx* c, const uint8_t* in, uint8_t* out, int8_t* status, size_t n, int64_t budget,
+                   sdk::Prop32Args* a) {
+    HIPCALL(hipMemsetAsync(c->p32_ctl.p, 0, kCtlBytes, c->stream));
+    HIPCALL(hipMemsetAsync(c->p32_list.p, 0, 4, c->stream));
+    *a = sdk::Prop32Args{};
+    a->in = in;
+    a->out = out;
+    a->status = status;
+    a->n = n;
+    a->heads = static_cast<uint32_t*>(c->p32_ctl.p);
+    a->list = static_cast<uint32_t*>(c->p32_list.p);
+    a->list_in = static_cast<uint8_t*>(c->p32_in.p);
+    // the search continues from the propagated grids when no node budget applies (a budget counts
+    // nodes from the input, so the statuses of budget hits would differ)
+    a->handover = (c->prop32_handover && budget == 0) ? 1 : 0;
+    return SDK_OK;
+}
+
+// The boards pass `a` listed (the list's length is on the device) through launch_solve -- `rest`
+// names order, budget, donate and solver; the buffers are filled in here -- and their answers
+// scattered back into the pass's out and status.
+int p32_fallback(sdk_ctx* c, const sdk::Prop32Args& a, SolveCall rest) {
+    rest.in = a.list_in;
+    rest.out = static_cast<uint8_t*>(c->p32_out.p);
+    rest.status = static_cast<int8_t*>(c->p32_st.p);
+    rest.n = a.n;
+    rest.n_dev = a.list;
+    int rc = launch_solve(c, rest);
+    if (rc) return rc;
+    // one thread per 4 bytes of the list's boards (its length is on the device: sized for all n)
+    if (sdk::launch_p32_scatter(rest.n_dev, rest.out, rest.status, a.in, a.out, a.status,
+                                grid_for(c, a.n * 81, 1024, 8), c->stream) != hipSuccess)
+        return fail(SDK_EHIP, "prop32 scatter launch failed");
+    return SDK_OK;
+}
+
 // The prop32 pass (prop32_kernel.h) over the batch, then the boards it leaves undecided -- listed
 // with their inputs on the device -- solved by the usual path (solve4, phased with donation when
 // that applies) with the list's length read on the device, and their answers scattered back.
@@ -970,29 +1021,14 @@ int launch_solve(sdk_ctx* c, const SolveCall& call) {
 int launch_prop32_solve(sdk_ctx* c, const SolveCall& s) {
     const size_t n = s.n;
     int rc;
-    constexpr size_t kCtlBytes = (size_t)sdk::kP32Heads * sdk::kP32HeadStride * 4;
-    if ((rc = ensure(c->p32_ctl, kCtlBytes)) || (rc = ensure(c->p32_list, (n + 1) * 4)) ||
-        (rc = ensure(c->p32_in, n * 81)) || (rc = ensure(c->p32_out, n * 81)) || (rc = ensure(c->p32_st, n)))
-        return rc;
-    HIPCALL(hipMemsetAsync(c->p32_ctl.p, 0, kCtlBytes, c->stream));
-    HIPCALL(hipMemsetAsync(c->p32_list.p, 0, 4, c->stream));
+    sdk::Prop32Args a;
+    if ((rc = p32_reserve(c, n)) || (rc = p32_pass_begin(c, s.in, s.out, s.status, n, s.budget, &a))) return rc;
     // SDK_OPT_TIMING: two spans, the pass itself and its fallback (search + scatter) as one
     hipEvent_t stop;
     if ((rc = timer_begin(c, &stop))) return rc;
-    sdk::Prop32Args a{};
-    a.in = s.in;
-    a.out = s.out;
-    a.status = s.status;
-    a.n = n;
-    a.heads = static_cast<uint32_t*>(c->p32_ctl.p);
-    a.list = static_cast<uint32_t*>(c->p32_list.p);
-    a.list_in = static_cast<uint8_t*>(c->p32_in.p);
     a.lc_every = (uint32_t)std::max(1, c->prop32_lc & 0xFF);
     a.lc_first = (c->prop32_lc >> 8) ? (uint32_t)(c->prop32_lc >> 8) : a.lc_every;
     a.max_steps = 96;
-    // the search continues from the propagated grids when no node budget applies (a budget counts
-    // nodes from the input, so the statuses of budget hits would differ)
-    a.handover = (c->prop32_handover && s.budget == 0) ? 1 : 0;
     a.tail_live = a.handover ? (uint32_t)c->prop32_tail_live : 0u;
     a.tail_step = (uint32_t)c->prop32_tail_step;
     const unsigned grid = grid_for(c, n, 64, 20);   // a group of 64 boards per dequeue
@@ -1006,20 +1042,12 @@ int launch_prop32_solve(sdk_ctx* c, const SolveCall& s) {
     TimedSpan span(c);
     if ((rc = timer_end(c, stop)) || (rc = span.begin())) return rc;
     c->prop32_ran = true;
-    SolveCall rest = s;     // the same order, budget, donate and solver over the list's boards
-    rest.in = static_cast<uint8_t*>(c->p32_in.p);
-    rest.out = static_cast<uint8_t*>(c->p32_out.p);
-    rest.status = static_cast<int8_t*>(c->p32_st.p);
-    rest.n_dev = static_cast<const uint32_t*>(c->p32_list.p);
-    rest.in_step = 1;
-    rc = launch_solve(c, rest);
-    if (!rc) {
-        // one thread per 4 bytes of the list's boards (its length is on the device: sized for all n)
-        if (sdk::launch_p32_scatter(rest.n_dev, rest.out, rest.status, s.in, s.out, s.status,
-                                    grid_for(c, n * 81, 1024, 8), c->stream) != hipSuccess)
-            rc = fail(SDK_EHIP, "prop32 scatter launch failed");
-    }
-    return span.end(rc);
+    SolveCall rest;     // the same order, budget, donate and solver over the list's boards
+    rest.order = s.order;
+    rest.budget = s.budget;
+    rest.donate = s.donate;
+    rest.solver = s.solver;
+    return span.end(p32_fallback(c, a, rest));
 }
 
 // Classify launch (sdk_classify_batch): the solve path with ORDER_CLASSIFY -- the prop32 pass under
@@ -1063,11 +1091,9 @@ int launch_grade(sdk_ctx* c, const uint8_t* d_in, uint8_t* d_out, int8_t* d_stat
     if (budget < 0) budget = (int64_t)c->budget;
     const uint64_t cap = std::min<uint64_t>(n, kDnCapBoards);
     const bool in_place = d_in == d_out;
-    constexpr size_t kCtlBytes = (size_t)sdk::kP32Heads * sdk::kP32HeadStride * 4;
     int rc;
-    if ((rc = ensure(c->p32_ctl, kCtlBytes)) || (rc = ensure(c->p32_list, (cap + 1) * 4)) ||
-        (rc = ensure(c->p32_in, cap * 81)) || (rc = ensure(c->p32_out, cap * 81)) || (rc = ensure(c->p32_st, cap)) ||
-        (in_place && (rc = ensure(c->gr_in, cap * 81))) || (!d_open && (rc = ensure(c->gr_open, cap))))
+    if ((rc = p32_reserve(c, cap)) || (in_place && (rc = ensure(c->gr_in, cap * 81))) ||
+        (!d_open && (rc = ensure(c->gr_open, cap))))
         return rc;
     TimedSpan span(c);
     if ((rc = span.begin())) return rc;
@@ -1078,35 +1104,21 @@ int launch_grade(sdk_ctx* c, const uint8_t* d_in, uint8_t* d_out, int8_t* d_stat
             HIPCALL(hipMemcpyAsync(c->gr_in.p, in, m * 81, hipMemcpyDeviceToDevice, c->stream));
             in = static_cast<const uint8_t*>(c->gr_in.p);
         }
-        HIPCALL(hipMemsetAsync(c->p32_ctl.p, 0, kCtlBytes, c->stream));
-        HIPCALL(hipMemsetAsync(c->p32_list.p, 0, 4, c->stream));
         sdk::Grade32Args a{};
-        a.p.in = in;
-        a.p.out = d_out + b0 * 81;
-        a.p.status = d_status + b0;
-        a.p.n = m;
-        a.p.heads = static_cast<uint32_t*>(c->p32_ctl.p);
-        a.p.list = static_cast<uint32_t*>(c->p32_list.p);
-        a.p.list_in = static_cast<uint8_t*>(c->p32_in.p);
-        // (a budget counts nodes from the input: launch_prop32_solve)
-        a.p.handover = (c->prop32_handover && budget == 0) ? 1 : 0;
+        if ((rc = p32_pass_begin(c, in, d_out + b0 * 81, d_status + b0, m, budget, &a.p))) break;
         a.level = d_level + b0;
         a.open = d_open ? d_open + b0 : static_cast<uint8_t*>(c->gr_open.p);
         HIPCALL(sdk::launch_grade32(a, grid_for(c, m, 64, 20), c->stream));
         c->prop32_ran = true;
-        SolveCall rest{a.p.list_in, nullptr, static_cast<uint8_t*>(c->p32_out.p), static_cast<int8_t*>(c->p32_st.p),
-                       nullptr, (size_t)m};
-        rest.n_dev = a.p.list;
+        SolveCall rest;
         rest.order = sdk::ORDER_CLASSIFY;
         rest.solver = SDK_SOLVER_QUAD;
         rest.budget = budget;
         rest.donate = 0;
-        if ((rc = launch_solve(c, rest))) break;
-        if (sdk::launch_p32_scatter(rest.n_dev, rest.out, rest.status, a.p.in, a.p.out, a.p.status,
-                                    grid_for(c, m * 81, 1024, 8), c->stream) != hipSuccess ||
-            sdk::launch_g32_verdict(rest.n_dev, rest.status, a.level, a.open, grid_for(c, m, 256, 8), c->stream) !=
-                hipSuccess)
-            rc = fail(SDK_EHIP, "grade scatter launch failed");
+        if ((rc = p32_fallback(c, a.p, rest))) break;
+        if (sdk::launch_g32_verdict(a.p.list, static_cast<const int8_t*>(c->p32_st.p), a.level, a.open,
+                                    grid_for(c, m, 256, 8), c->stream) != hipSuccess)
+            rc = fail(SDK_EHIP, "grade verdict launch failed");
     }
     return span.end(rc);
 }
