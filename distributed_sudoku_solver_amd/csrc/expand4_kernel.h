@@ -7,8 +7,9 @@
 // picks its branch exactly as expand_kernel does -- contradiction: no child; solved: a leaf
 // (count mode) or itself as its only child (first-solution mode); open: the MRV cell (count
 // mode) or the lowest open cell (first-solution mode), children in ascending digit order.
-// The frontier it builds is therefore the same array, byte for byte (GPU test).  Boards are
-// assigned grid-stride, four per wave, with no dequeue atomics.
+// The frontier it builds is therefore the same array, byte for byte (tests/test_gpu_frontier.py
+// against expand_kernel, tests/test_gpu_frontier_model.py both against the scalar model).  Boards
+// are assigned grid-stride, four per wave, with no dequeue atomics.
 #pragma once
 #include "frontier_args.h"
 #include "solve4_kernel.h"
@@ -34,7 +35,8 @@ __device__ __forceinline__ void expand4_load(const Lane4& w, const ExpandArgs& a
     const uint32_t s0 = on ? cell_s4(i0) : kInert4, s1 = on ? cell_s4(i1) : kInert4, s2 = on ? cell_s4(i2) : kInert4;
     if (valid && a.mask) {
         // level 0: each board's TASK `range` on its lowest-index empty input cell
-        // (DHT_Node.py:474,522,531)
+        // (DHT_Node.py:474,522,531).  An empty range leaves that cell X = S = 0: round4<false>'s
+        // empty-cell test reports it in the first round, so the board has no child (as expand_kernel)
         const uint32_t fm = ((uint32_t)a.mask[i] >> 1) & kCands;
         uint32_t z = ~0u;
         if (w.act) z = i0 == 0 ? (uint32_t)w.c0 : (i1 == 0 ? (uint32_t)w.c0 + 27 : (i2 == 0 ? (uint32_t)w.c0 + 54 : ~0u));
