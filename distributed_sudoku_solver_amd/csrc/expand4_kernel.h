@@ -108,7 +108,6 @@ __device__ __forceinline__ void expand4_out(const Lane4& w, const ExpandArgs& a,
     }
 }
 
-#ifdef SDK_DEFINE_SOLVE4_KERNEL
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SDK_SOLVE4_WAVES_PER_EU))) void expand4_kernel(ExpandArgs a) {
     __shared__ uint2 s_region[2 * kRegion4];
     __shared__ uint8_t s_in[2 * 2 * 81];
@@ -156,6 +155,5 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SDK_SOLVE4_W
     if (threadIdx.x == 0 && tl) atomicAdd(&a.ctl->lvl_leaves, (unsigned long long)tl);
     if (threadIdx.x == 0 && to) atomicAdd(&a.ctl->open, (unsigned long long)to);
 }
-#endif
 
 }  // namespace sdk

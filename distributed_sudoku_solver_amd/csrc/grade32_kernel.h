@@ -50,19 +50,12 @@ namespace sdk {
 
 constexpr uint32_t kG32MaxSteps = 768;   // > 729 + 3 (see above)
 
-struct Grade32Args {
-    Prop32Args p;        // in, out, status, n, heads, list, list_in, handover (no schedule, no tail)
-    uint8_t* level;      // [n]
-    uint8_t* open;       // [n]
-};
-
 // SDK_GRADE32_STATS (profiling builds only): per group, histograms of the unit/cells steps it ran and
 // of its locked passes (tools/bench_grade.py --stats reads them)
 #ifndef SDK_GRADE32_STATS
 #define SDK_GRADE32_STATS 0
 #endif
 
-#ifdef SDK_DEFINE_GRADE32_KERNEL
 #if SDK_GRADE32_STATS
 __device__ unsigned long long g_g32_stats[2][128];
 #define G32_STAT(k, v) atomicAdd(&g_g32_stats[k][min((uint32_t)(v), 127u)], 1ull)
@@ -180,6 +173,5 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) void gr
         p32_group_end(a, w, x, lds, G, handed);
     }
 }
-#endif
 
 }  // namespace sdk

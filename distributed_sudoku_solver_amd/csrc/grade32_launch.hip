@@ -1,7 +1,6 @@
 // grade32_launch.hip -- translation unit of grade32_kernel (the propagation pass as a grader, one
 // technique set at a time; see grade32_kernel.h)
-#define SDK_NO_SOLVE_KERNEL
-#define SDK_DEFINE_GRADE32_KERNEL
+#include "launch.h"
 #include "grade32_kernel.h"
 
 namespace sdk {

@@ -48,6 +48,7 @@
 // every cell is closed and no unit misses a digit (then each unit holds each digit once).
 #pragma once
 #include "solve_kernel.h"
+#include "prop32_args.h"
 
 namespace sdk {
 
@@ -62,26 +63,6 @@ constexpr uint32_t kP32Region = 3456;    // bytes per half: 81 cell records + th
                                          // (= 32 boards x 108 B of the answers' staging, p32_stage_byte)
 constexpr uint32_t kP32Table = 2 * kP32Region;   // p32_unit's read order, 40 B per lane (p32_order_table)
 constexpr uint32_t kP32Lds = kP32Table + 64 * 40;
-constexpr uint32_t kP32Heads = 8;        // dequeue counters, one per XCD segment of the groups
-constexpr uint32_t kP32HeadStride = 32;  // words between counters (own cache lines)
-
-struct Prop32Args {
-    const uint8_t* in;       // boards [n][81]; 16-byte aligned
-    uint8_t* out;            // [n][81]; 16-byte aligned
-    int8_t* status;          // [n]: 1 solved, 0 no completion, kStUndecided
-    uint64_t n;
-    uint32_t* heads;         // kP32Heads counters kP32HeadStride words apart (zeroed)
-    uint32_t* list;          // [0] undecided boards, then their indices (list[0] zeroed)
-    uint8_t* list_in;        // the undecided boards' inputs, dense, in list order
-    uint32_t lc_every;       // a locked-candidates pass after step lc_first, then every lc_every-th
-    uint32_t lc_first;       // step (lc_first = lc_every: after every lc_every-th step)
-    uint32_t max_steps;      // boards still live after this many steps are undecided
-    int handover;            // the list gets an undecided board's propagated grid (its closed cells
-                             // filled in: the same completions) instead of its input; not for
-                             // boards with a duplicated or out-of-domain given
-    uint32_t tail_live;      // handover: from step tail_step on, a group with at most this many
-    uint32_t tail_step;      // live boards hands them to the search and ends (0 = never)
-};
 
 // OR / AND over the 32 lanes of each half, result in every lane of the half: rotations inside
 // each row of 16 (DPP), then the two rows of each half combined -- v_permlane16_swap (gfx950: the
@@ -895,39 +876,6 @@ __device__ unsigned long long g_p32_stats[4][128];
 #define P32_STAT(k, v) ((void)0)
 #endif
 
-#ifdef SDK_DEFINE_PROP32_KERNEL
-// The fallback's answers back into the batch: listed board i is board list[1 + i]; a board the search
-// did not solve gets its own input back (DHT_Node.py:535), not the propagated grid it was searched from.
-// One thread per 4 bytes of the dense answers (one dword load; 32-bit index math: the list holds at most
-// 2^24 boards), grid-stride over the whole list.
-__global__ void p32_scatter_kernel(const uint32_t* list, const uint8_t* sub_out, const int8_t* sub_st,
-                                   const uint8_t* in, uint8_t* out, int8_t* status) {
-    const uint32_t total = list[0] * 81u;
-    for (uint32_t e0 = 4u * (blockIdx.x * blockDim.x + threadIdx.x); e0 < total; e0 += 4u * gridDim.x * blockDim.x) {
-        uint32_t word;
-        if (e0 + 4u <= total) {
-            word = *reinterpret_cast<const uint32_t*>(sub_out + e0);
-        } else {
-            word = 0u;
-            for (uint32_t b = 0; e0 + b < total; ++b) word |= (uint32_t)sub_out[e0 + b] << (8 * b);
-        }
-#pragma unroll
-        for (uint32_t b = 0; b < 4u; ++b) {
-            const uint32_t e = e0 + b;
-            if (e >= total) break;
-            const uint32_t i = e / 81u, c = e - 81u * i;
-            const uint32_t j = list[1 + i];
-            const int8_t st = sub_st[i];
-            const uint64_t o = (uint64_t)j * 81u + c;
-            out[o] = st == 1 ? (uint8_t)(word >> (8 * b)) : in[o];
-            if (c == 0) status[j] = st;
-        }
-    }
-}
-
-#endif
-
-#if defined(SDK_DEFINE_PROP32_KERNEL) || defined(SDK_DEFINE_GRADE32_KERNEL)
 // kP32Order (see p32_unit): digit class t of a Sudoku solution with cell indices distinct mod 32
 // in every class (static: the grading pass's translation unit, grade32_kernel.h, has its own copy)
 static __constant__ uint8_t kP32Order[81] = {2, 5, 8, 1, 4, 7, 3, 0, 6, 1, 4, 7, 0, 3, 6, 2, 8, 5, 0, 3, 6, 8, 2, 5, 1,
@@ -965,126 +913,5 @@ __device__ __forceinline__ P32Lane p32_wave_begin(p32_lds_t* lds) {
     w.reg = lds + w.half * kP32Region;
     return w;
 }
-
-#endif
-
-#ifdef SDK_DEFINE_PROP32_KERNEL
-#ifndef SDK_PROP32_WAVES_PER_EU
-#define SDK_PROP32_WAVES_PER_EU 4
-#endif
-// The kernel body; kStamp (prop32_clock_kernel, a diagnostic twin: the timed kernel runs no stamp)
-// writes s_memtime (shader clock) and s_memrealtime (100 MHz) at a workgroup's entry and exit to
-// stamps[4 blockIdx.x ..], a buffer nothing else reads: the in-kernel clock of a launch is
-// their ratio (MI355X_MICROARCH.md, "DVFS give-back" item 6), the clock the VALU roofline prices
-template <bool kStamp>
-__device__ __forceinline__ void prop32_body(Prop32Args a, uint64_t* stamps) {
-    __shared__ __attribute__((aligned(16))) uint8_t s_lds[kP32Lds];
-    p32_lds_t* const lds = (p32_lds_t*)s_lds;
-    if (kStamp && threadIdx.x == 0) {    // (stored at once: no register holds them through the loop)
-        uint64_t* o = stamps + 4u * blockIdx.x;
-        o[0] = __builtin_amdgcn_s_memtime();
-        o[1] = __builtin_amdgcn_s_memrealtime();
-    }
-    const P32Lane w = p32_wave_begin(lds);
-    const uint32_t groups = (uint32_t)((a.n + 63) / 64);
-    uint32_t seg = blockIdx.x % kP32Heads;
-    for (;;) {
-        const uint32_t g = p32_dequeue(a, groups, seg);
-        if (g == ~0u) break;
-        P32Cells x;
-        P32Group G;
-        p32_group_begin(a, w, g, x, G);
-        uint64_t fixw = 0ull;              // live boards unchanged by the step before this locked pass
-        bool lc = false;
-        uint32_t next_lc = a.lc_first;     // the step after which the next locked-candidates pass runs
-#if SDK_PROP32_STATS
-        uint32_t st_lc = 0, st_t4 = ~0u, st_t1 = ~0u;
-#endif
-        uint32_t it = 0;
-        p32_run(G, [&]() {
-            uint32_t empty, alls;
-            p32_singles(w, x, empty, alls);
-            __builtin_amdgcn_wave_barrier();
-            if (lc) {
-#if SDK_PROP32_STATS
-                ++st_lc;
-#endif
-                const uint32_t lc_own = p32_locked(w, x);
-                const uint64_t lchg = p32_mask64(p32_half_or(w.act ? lc_own : 0u));
-                const uint64_t stuck = fixw & ~lchg & G.live;
-                G.undec |= stuck;
-                G.live &= ~stuck;
-                fixw = 0ull;
-                lc = false;
-                __builtin_amdgcn_wave_barrier();
-                return;
-            }
-            p32_decide(w, lds, it == 0, empty, alls, G);
-#if SDK_PROP32_STATS
-            if (st_t4 == ~0u && __builtin_popcountll(G.live) <= 4) st_t4 = it;
-            if (st_t1 == ~0u && __builtin_popcountll(G.live) <= 1) st_t1 = it;
-#endif
-            if (G.live != 0ull) {
-                if (a.tail_live && it >= a.tail_step && (uint32_t)__builtin_popcountll(G.live) <= a.tail_live) {
-                    G.undec |= G.live;   // the last few boards go to the search with their propagated grids
-                    G.live = 0ull;
-                } else if (++it >= a.max_steps) {
-                    G.undec |= G.live;
-                    G.live = 0ull;
-                }
-            }
-            __builtin_amdgcn_wave_barrier();
-            // step lc_first and every lc_every-th after it are followed by a locked-candidates pass;
-            // that step also reports which boards it left unchanged (a board unchanged by it and by
-            // the pass is stuck)
-            lc = G.live != 0ull && it == next_lc;
-            if (lc) next_lc += a.lc_every;
-            if (lc) {
-                const uint32_t chg_own = p32_cells<true>(w, x);
-                fixw = G.live & ~p32_mask64(p32_half_or(w.act ? chg_own : 0u));
-            } else {
-                (void)p32_cells<false>(w, x);
-            }
-            __builtin_amdgcn_wave_barrier();
-        });
-#if SDK_PROP32_STATS
-        if (threadIdx.x == 0) {
-            P32_STAT(0, it);
-            P32_STAT(1, st_t4);
-            P32_STAT(2, st_t1);
-            P32_STAT(3, st_lc);
-        }
-#endif
-        __builtin_amdgcn_wave_barrier();
-        uint64_t handed = a.handover ? G.undec & ~G.inexact : 0ull;   // listed with their grids
-        if (handed) {
-            uint32_t empty, alls;
-            p32_singles(w, x, empty, alls);
-            __builtin_amdgcn_wave_barrier();
-            (void)p32_refute_handed(w, lds, G, handed);
-            __builtin_amdgcn_wave_barrier();
-        }
-        p32_group_end(a, w, x, lds, G, handed);
-    }
-    if (kStamp) {
-        const uint64_t t1 = __builtin_amdgcn_s_memtime(), r1 = __builtin_amdgcn_s_memrealtime();
-        if (threadIdx.x == 0) {
-            uint64_t* o = stamps + 4u * blockIdx.x;
-            o[2] = t1;
-            o[3] = r1;
-        }
-    }
-}
-
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SDK_PROP32_WAVES_PER_EU))) void prop32_kernel(
-    Prop32Args a) {
-    prop32_body<false>(a, nullptr);
-}
-
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SDK_PROP32_WAVES_PER_EU))) void prop32_clock_kernel(
-    Prop32Args a, uint64_t* stamps) {
-    prop32_body<true>(a, stamps);
-}
-#endif
 
 }  // namespace sdk

@@ -1,8 +1,7 @@
 // solve4_launch.hip -- separate translation unit for solve4_kernel (four boards per
 // wave, two per 16-bit half of every word), built like solve2_launch.hip with
 // -mllvm -simplifycfg-sink-common=false (see Makefile).
-#define SDK_NO_SOLVE_KERNEL
-#define SDK_DEFINE_SOLVE4_KERNEL
+#include "launch.h"
 #include "solve4_kernel.h"
 #include "expand4_kernel.h"
 

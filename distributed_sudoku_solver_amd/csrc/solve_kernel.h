@@ -43,6 +43,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "solve_args.h"
 
 // Three-input OR and and-or in the kernels' inline asm.  v_or3_b32 and v_and_or_b32 (like every
 // older 3-source VOP3 op) issue at most ~1 per SIMD quad-cycle whatever the operands; the same
@@ -72,69 +73,8 @@ constexpr uint32_t kCands = 0x1FFu;
 constexpr uint32_t kClue = 0x200u;
 constexpr uint32_t kInert = 0x400u;
 constexpr uint32_t kFixed = kClue | kInert;
-constexpr int kMaxDepth = 81;
-constexpr uint32_t kChunk = 4;        // expand_kernel chunk; solve_kernel takes SolveArgs::chunk
-constexpr int kStackWordsPerBlock = kMaxDepth * 64;
 
 enum { P_CONTRA = 0, P_SOLVED = 1, P_OPEN = 2 };
-// ORDER_CLASSIFY (sdk_classify_batch, QUAD solver only; not an SDK_ORDER_*): MRV search for at most
-// two completions like ORDER_MRV, but the second one ends the board as kStMultiple with its input
-// restored instead of starting the LEX re-search
-enum { ORDER_MRV = 0, ORDER_LEX = 1, ORDER_CLASSIFY = 2 };
-
-struct SolveArgs {
-    const uint8_t* in;
-    const uint16_t* mask;      // nullable: first-cell digit mask, bit d = digit d
-    uint8_t* out;
-    int8_t* status;
-    uint64_t* work;            // nullable
-    uint64_t n;
-    uint32_t* next;            // work counter (zeroed before launch)
-    uint32_t* stack;           // gridDim.x * kStackWordsPerBlock words
-    uint64_t budget;           // nodes per board, 0 = unlimited
-    int order;                 // SDK_ORDER_*, or ORDER_CLASSIFY
-    uint64_t limit;            // count mode: per-board completion limit (0 = none)
-    unsigned long long* count; // count mode: running total over the batch (atomic)
-    unsigned long long* counts;// count mode: per-board counts (nullable)
-    int count_mode;
-    uint32_t chunk;            // boards per dequeue (one atomic on `next` per chunk)
-    int work_rounds;           // what work[] counts: 0 search nodes, 1 propagation rounds, 2 max DFS depth
-    uint64_t in_first;         // board i of the launch reads in[(in_first + i*in_step)*81];
-    uint64_t in_step;          // outputs stay dense (out[i*81], status[i]); 0/1 = contiguous
-    int locked;                // QUAD solver: locked-candidates pass at fixpoints (SDK_OPT_LOCKED)
-    uint32_t* heads;           // QUAD solver: kHeads dequeue heads, one per XCD segment (nullable)
-    void* donate;              // QUAD solver, LEX solves: subtree-donation area (solve4_kernel.h, DnCtl first)
-    const uint32_t* n_dev;     // donation kernel: board count read on the device (a phase's list
-                               // length, written by an earlier launch); `n` is then its bound
-    void* save = nullptr;      // QUAD split phase: stacks of boards that reach the split budget
-                               // (solve4_kernel.h SplitSave; nullable)
-    uint32_t* save_idx = nullptr;   // ... and each saved board's entry (by board index)
-    uint64_t budget_big = 0;        // QUAD split phase of a device-counted batch (n_dev): the budget
-                                    // when more than kBudgetBigBoards boards are searched (0 = budget)
-    long long* found = nullptr;     // QUAD first-solution scan (sdk_frontier_first): the lowest board
-                                    // index (in_first + i * in_step) with status 1 or -2 so far; boards
-                                    // above it are cancelled (solve4_kernel.h, s_found4)
-};
-// the phased solve's default split budget doubles above this many searched boards (sudoku_hip.hip)
-constexpr uint64_t kBudgetBigBoards = 1ull << 19;
-// status of a board a first-solution scan stopped because it lies above a lower board's hit
-constexpr int kStCancelled = -3;
-// status of a classified board with at least two completions (SDK_MULTIPLE)
-constexpr int kStMultiple = 2;
-
-// per-XCD dequeue: the first n - n/128 boards are cut into kHeads contiguous segments with a
-// head each, workgroup g takes chunks of segment g % kHeads (the XCD the round-robin
-// dispatch put it on) and, once that is drained, of the shared tail (one more head);
-// heads kHeadStride words apart (own cache lines)
-#ifndef SDK_HEADS
-#define SDK_HEADS 8
-#endif
-constexpr int kHeads = SDK_HEADS;   // a multiple of 8: segment g % kHeads stays on one XCD
-constexpr int kHeadStride = 64;
-// the heads buffer: kHeads segment heads, the shared tail, then the launch's dequeue counter, so
-// one memset clears a QUAD launch's dequeue state
-constexpr int kHeadNext = (kHeads + 1) * kHeadStride;
-constexpr int kHeadWords = (kHeads + 2) * kHeadStride;
 
 __device__ __forceinline__ uint32_t cell_init(uint32_t v) {
     return v == 0 ? kCands : (v <= 9 ? ((1u << (v - 1)) | kClue) : kInert);
@@ -349,69 +289,5 @@ __device__ __forceinline__ void init_wave(Wave& w, uint32_t* s_cell, uint32_t* s
         w.ucell[k] = cell;
     }
 }
-
-#ifndef SDK_NO_SOLVE_KERNEL   // solve2_launch.hip takes the helpers only
-__global__ __launch_bounds__(64, 8) void solve_kernel(SolveArgs a) {
-    __shared__ uint32_t s_cell[96];
-    __shared__ uint32_t s_unit[32];
-    __shared__ uint32_t s_br[kMaxDepth];
-    Wave w;
-    init_wave(w, s_cell, s_unit, s_br);
-    w.stk = a.stack + (size_t)blockIdx.x * kStackWordsPerBlock;
-    const int lane = w.lane;
-    for (;;) {
-        uint32_t base = 0;
-        if (lane == 0) base = atomicAdd(a.next, a.chunk);
-        base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
-        if ((uint64_t)base >= a.n) break;
-        const uint64_t end = min((uint64_t)base + a.chunk, a.n);
-        for (uint64_t i = base; i < end; ++i) {
-            const uint8_t* src = a.in + (a.in_first + i * a.in_step) * 81;
-            const uint32_t inA = src[lane];
-            const uint32_t inB = w.hasB ? (uint32_t)src[64 + lane] : 0u;
-            uint32_t sa = cell_init(inA);
-            uint32_t sb = w.hasB ? cell_init(inB) : kInert;
-            // TASK `range` restricts the lowest-index empty input cell only (DHT_Node.py:474,522,531)
-            const uint32_t fm = a.mask ? (((uint32_t)a.mask[i] >> 1) & kCands) : kCands;
-            const unsigned long long za = __ballot(inA == 0);
-            const unsigned long long zb = __ballot(w.hasB && inB == 0);
-            if (za) {
-                if (lane == (int)__builtin_ctzll(za)) sa &= fm | ~kCands;
-            } else if (zb) {
-                if (lane == (int)__builtin_ctzll(zb)) sb &= fm | ~kCands;
-            }
-            uint8_t* dst = a.out ? a.out + i * 81 : nullptr;
-            uint64_t nodes = 0, rounds = 0, maxd = 0;
-            int8_t st;
-            // count mode: whole-subtree count (order-independent, so MRV); the
-            // batch stops early once the running total reaches the limit.
-            // solve mode: MRV search for <= 2 completions, or LEX for the first.
-            bool skip = false;
-            if (a.count_mode && a.limit) {
-                unsigned long long tot = 0;
-                if (lane == 0) tot = __hip_atomic_load(a.count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                tot = __shfl(tot, 0);
-                skip = tot >= a.limit;
-            }
-            const int order0 = (a.count_mode || a.order != ORDER_LEX) ? ORDER_MRV : ORDER_LEX;
-            const uint64_t lim0 = a.count_mode ? a.limit : (order0 == ORDER_LEX ? 1u : 2u);
-            int64_t c = 0;
-            if (!skip) c = search(w, order0, sa, sb, lim0, a.budget, nodes, rounds, maxd, dst, inA, inB);
-            if (!a.count_mode && order0 == ORDER_MRV && c >= 2)
-                c = search(w, ORDER_LEX, sa, sb, 1, a.budget, nodes, rounds, maxd, dst, inA, inB);
-            if (a.count_mode && lane == 0) {
-                if (c > 0) atomicAdd(a.count, (unsigned long long)c);
-                if (a.counts) a.counts[i] = (unsigned long long)(c < 0 ? 0 : c);
-            }
-            st = c < 0 ? (int8_t)-2 : (c > 0 ? (int8_t)1 : (int8_t)0);
-            if (dst && c <= 0) write_board(w, dst, inA, inB, sa, sb, false);
-            if (lane == 0) {
-                if (a.status) a.status[i] = st;
-                if (a.work) a.work[i] = a.work_rounds == 1 ? rounds : (a.work_rounds == 2 ? maxd : nodes);
-            }
-        }
-    }
-}
-#endif  // SDK_NO_SOLVE_KERNEL
 
 }  // namespace sdk

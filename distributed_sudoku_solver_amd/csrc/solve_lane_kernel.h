@@ -29,7 +29,6 @@
 
 namespace sdk {
 
-constexpr int kLaneThreads = 256;          // 4 independent waves per workgroup
 constexpr int kLaneSteps = 32;             // DFS steps between refills
 constexpr uint32_t kLaneAll = 0x3FEu;      // digits 1..9 as bits 1..9 (the oracle's layout)
 
@@ -41,7 +40,6 @@ struct LaneLds {
 __device__ __forceinline__ uint32_t lane_row(uint32_t p) { return (p * 57u) >> 9; }   // p / 9 for p < 81
 __device__ __forceinline__ uint32_t lane_div3(uint32_t x) { return (x * 11u) >> 5; }  // x / 3 for x < 9
 
-#ifdef SDK_DEFINE_LANE_KERNEL
 __global__ __launch_bounds__(kLaneThreads) void solve_lane_kernel(SolveArgs a) {
     __shared__ LaneLds s_lane[kLaneThreads / 64];
     const int lane = threadIdx.x & 63;
@@ -181,6 +179,5 @@ __global__ __launch_bounds__(kLaneThreads) void solve_lane_kernel(SolveArgs a) {
         }
     }
 }
-#endif  // SDK_DEFINE_LANE_KERNEL
 
 }  // namespace sdk

@@ -18,30 +18,13 @@
 #include <vector>
 
 #include "../../include/sudoku_hip.h"
+#include "launch.h"   // the solve, prop32 and grade32 kernels: their units' launch functions and *_args.h
+// the kernels this unit still compiles itself
 #include "check_kernel.h"
-#include "solve_kernel.h"
 #include "frontier_kernel.h"
-#include "solve2_kernel.h"   // constants only: the kernel lives in solve2_launch.hip
-#include "solve4_kernel.h"   // constants only: the kernel lives in solve4_launch.hip
-#include "prop32_kernel.h"   // constants only: the kernel lives in prop32_launch.hip
-#include "grade32_kernel.h"  // constants only: the kernel lives in grade32_launch.hip
 #include "minimize_kernel.h"
 #include "generate_kernel.h"
-#define SDK_DEFINE_LANE_KERNEL
 #include "solve_lane_kernel.h"
-
-namespace sdk {
-hipError_t launch_solve2(const SolveArgs& a, unsigned grid, hipStream_t stream);
-hipError_t launch_solve4(const SolveArgs& a, unsigned grid, hipStream_t stream);
-int solve4_dn_blocks_per_cu();   // resident workgroups per CU of solve4_kernel<true>
-hipError_t launch_prop32(const Prop32Args& a, unsigned grid, hipStream_t stream, uint64_t* stamps);
-hipError_t launch_p32_scatter(const uint32_t* list, const uint8_t* sub_out, const int8_t* sub_st, const uint8_t* in,
-                              uint8_t* out, int8_t* status, unsigned grid, hipStream_t stream);
-hipError_t launch_grade32(const Grade32Args& a, unsigned grid, hipStream_t stream);
-hipError_t launch_g32_verdict(const uint32_t* list, const int8_t* sub_st, uint8_t* level, uint8_t* open,
-                              unsigned grid, hipStream_t stream);
-hipError_t launch_expand4(const ExpandArgs& a, unsigned grid, hipStream_t stream);   // expand4_kernel.h
-}
 
 namespace {
 
@@ -336,22 +319,22 @@ struct sdk_ctx {
     std::mutex mu;
     HostBuf stage;                 // pinned staging (see HostBuf)
     // options
-    int order = SDK_ORDER_LEX;     // lex-first DFS: no uniqueness proof needed (faster than MRV_UNIQUE, r02)
-    uint64_t budget = 0;
-    int waves_per_cu = 32;
-    int check_blocks_per_cu = 3;
-    int check_variant = SDK_CHECK_REG1;
-    int solve_chunk = 0;          // boards per dequeue, 0 = automatic
-    int work_rounds = 0;
-    int solver = SDK_SOLVER_QUAD;
-    int locked = 1;                // QUAD: locked candidates at fixpoints (fewer search nodes, same answers)
-    int waves_per_cu2 = 28;       // solve2/solve4 grid per CU = solve4's resident waves (7 per SIMD; a larger
+    int64_t order = SDK_ORDER_LEX;     // lex-first DFS: no uniqueness proof needed (faster than MRV_UNIQUE, r02)
+    int64_t budget = 0;
+    int64_t waves_per_cu = 32;
+    int64_t check_blocks_per_cu = 3;
+    int64_t check_variant = SDK_CHECK_REG1;
+    int64_t solve_chunk = 0;          // boards per dequeue, 0 = automatic
+    int64_t work_rounds = 0;
+    int64_t solver = SDK_SOLVER_QUAD;
+    int64_t locked = 1;                // QUAD: locked candidates at fixpoints (fewer search nodes, same answers)
+    int64_t waves_per_cu2 = 28;       // solve2/solve4 grid per CU = solve4's resident waves (7 per SIMD; a larger
                                   // grid only adds waves that start once the queue is drained: 1 % slower, r02)
     // workspaces
     DevBuf stack, counter, heads, in, mask, out, status, work, verdict;
     uint32_t heads_round = 0;      // launches since the heads pool was cleared (kHeadRounds regions)
-    int xcd_heads = 1;             // QUAD: per-XCD dequeue heads (SDK_OPT_XCD_HEADS)
-    int donate = 1;                // QUAD, LEX solves: subtree donation (SDK_OPT_DONATE)
+    int64_t xcd_heads = 1;             // QUAD: per-XCD dequeue heads (SDK_OPT_XCD_HEADS)
+    int64_t donate = 1;                // QUAD, LEX solves: subtree donation (SDK_OPT_DONATE)
     DevBuf dn;                     // two donation areas (solve4_kernel.h: DnCtl, records, items,
                                    // mailboxes), one per donation phase of a phased solve
     DnTail dn_tail[2];             // [0] the phased solve's tail boards (area 0), [1] its LEX re-solves (area 1)
@@ -364,22 +347,22 @@ struct sdk_ctx {
     bool dn_ran = false;           // the last solve was phased (dn_stat and `delivered` are its)
     bool prop32_ran = false;       // the last solve ran the prop32 pass (p32_list[0] = its undecided boards)
     bool dn_err_check = false;     // a phased solve ran since its control blocks' error words were read
-    int dn_fault = 0;              // SDK_OPT_DN_FAULT (test only)
-    int dn_helpers = 2;            // SDK_OPT_DONATE_HELPERS: donation-launch waves per listed board (+ 64)
-    int dn_resume = 1;             // SDK_OPT_DONATE_RESUME: split boards resume from their saved stacks
+    int64_t dn_fault = 0;              // SDK_OPT_DN_FAULT (test only)
+    int64_t dn_helpers = 2;            // SDK_OPT_DONATE_HELPERS: donation-launch waves per listed board (+ 64)
+    int64_t dn_resume = 1;             // SDK_OPT_DONATE_RESUME: split boards resume from their saved stacks
     DevBuf dn_save, dn_save_idx, dn_seeds;   // sdk::SplitSave, its entry per board, the seed list
-    int dn_exhaustive = 1;         // phase 2 in MRV count-to-2 order (SDK_OPT_DONATE_MODE)
+    int64_t dn_exhaustive = 1;         // phase 2 in MRV count-to-2 order (SDK_OPT_DONATE_MODE)
     int64_t dn_max = 1 << 19;      // largest batch solved in phases (SDK_OPT_DONATE_MAX, 0 = any)
     uint32_t dn_epoch = 0;         // launches that used it (mailbox / registration entries carry it)
     int dn_blocks_per_cu = 0;      // resident solve4_kernel<true> workgroups per CU (queried once)
-    int prop32 = 1;                // QUAD: bit-sliced root propagation first (SDK_OPT_PROP32)
-    int prop32_lc = 5 | (3 << 8);  // ... a locked-candidates pass every this many steps (low byte),
+    int64_t prop32 = 1;                // QUAD: bit-sliced root propagation first (SDK_OPT_PROP32)
+    int64_t prop32_lc = 5 | (3 << 8);  // ... a locked-candidates pass every this many steps (low byte),
                                    //     the first after step (value >> 8), 0 = the period: after
                                    //     steps 3, 8, 13, ... (prop32 "schedule")
     int64_t prop32_min = 4096;     // ... for batches of at least this many boards
-    int prop32_handover = 1;       // ... undecided boards searched from their propagated grids
-    int prop32_tail_live = 0;      // ... a group's last (at most this many) live boards handed over
-    int prop32_tail_step = 24;     //     from this step on (SDK_OPT_PROP32_TAIL = live | step << 8)
+    int64_t prop32_handover = 1;       // ... undecided boards searched from their propagated grids
+    int64_t prop32_tail_live = 0;      // ... a group's last (at most this many) live boards handed over
+    int64_t prop32_tail_step = 24;     //     from this step on (SDK_OPT_PROP32_TAIL = live | step << 8)
     DevBuf p32_ctl, p32_list, p32_in, p32_out, p32_st;
     int clock_probe = 0;           // sdk_debug_clock_arm: prop32 passes run the stamped twin
     DevBuf p32_stamps;             // ... its stamps, 4 words per workgroup of the last such pass
@@ -405,7 +388,7 @@ struct sdk_ctx {
     int comm_rank = 0;
     int comm_world = 1;
     // timing
-    bool timing = false;          // SDK_OPT_TIMING
+    int64_t timing = 0;           // SDK_OPT_TIMING
     bool timer_hold = false;      // a TimedSpan is open: the launches inside it are not timed apart
     std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
     size_t events_used = 0;
@@ -734,7 +717,7 @@ int launch_solve_once(sdk_ctx* c, const SolveCall& s, const SolvePhase& ph = {})
         // the resident grid, at most what the kernel keeps of it for n boards: n / 4 + 64 + helpers x
         // min(n, kDnHelpCap) (solve4_kernel; the list on the device may be shorter, then it keeps less)
         grid_used = (unsigned)std::max<uint64_t>(
-            1, std::min<uint64_t>({(uint64_t)c->cus * (uint64_t)std::min(c->dn_blocks_per_cu, c->waves_per_cu2),
+            1, std::min<uint64_t>({(uint64_t)c->cus * (uint64_t)std::min<int64_t>(c->dn_blocks_per_cu, c->waves_per_cu2),
                                    (uint64_t)sdk::kDnMbox,
                                    ((uint64_t)n + 3) / 4 + 64ull +
                                        (uint64_t)c->dn_helpers * std::min<uint64_t>(n, sdk::kDnHelpCap)}));
@@ -749,9 +732,8 @@ int launch_solve_once(sdk_ctx* c, const SolveCall& s, const SolvePhase& ph = {})
     } else if (two) {
         HIPCALL(sdk::launch_solve2(a, grid, c->stream));
     } else {
-        sdk::solve_kernel<<<grid, 64, 0, c->stream>>>(a);
+        HIPCALL(sdk::launch_solve1(a, grid, c->stream));
     }
-    HIPCALL(hipGetLastError());
     return timer_end(c, stop);
 }
 
@@ -1026,7 +1008,7 @@ int launch_prop32_solve(sdk_ctx* c, const SolveCall& s) {
     // SDK_OPT_TIMING: two spans, the pass itself and its fallback (search + scatter) as one
     hipEvent_t stop;
     if ((rc = timer_begin(c, &stop))) return rc;
-    a.lc_every = (uint32_t)std::max(1, c->prop32_lc & 0xFF);
+    a.lc_every = (uint32_t)std::max<int64_t>(1, c->prop32_lc & 0xFF);
     a.lc_first = (c->prop32_lc >> 8) ? (uint32_t)(c->prop32_lc >> 8) : a.lc_every;
     a.max_steps = 96;
     a.tail_live = a.handover ? (uint32_t)c->prop32_tail_live : 0u;
@@ -1571,128 +1553,6 @@ int sdk_destroy(sdk_ctx* c) {
     return SDK_OK;
 }
 
-int sdk_set_option(sdk_ctx* c, int key, int64_t value) {
-    if (!c) return fail(SDK_EINVAL, "ctx is NULL");
-    std::lock_guard<std::mutex> lk(c->mu);
-    switch (key) {
-        case SDK_OPT_ORDER:
-            if (value != SDK_ORDER_MRV_UNIQUE && value != SDK_ORDER_LEX) return fail(SDK_EINVAL, "bad order %lld", (long long)value);
-            c->order = (int)value;
-            return SDK_OK;
-        case SDK_OPT_NODE_BUDGET:
-            if (value < 0) return fail(SDK_EINVAL, "budget must be >= 0");
-            c->budget = (uint64_t)value;
-            return SDK_OK;
-        case SDK_OPT_WAVES_PER_CU:
-            if (value < 1 || value > 32) return fail(SDK_EINVAL, "waves per CU must be 1..32");
-            c->waves_per_cu = (int)value;
-            return SDK_OK;
-        case SDK_OPT_CHECK_BLOCKS_PER_CU:
-            if (value < 1 || value > 16) return fail(SDK_EINVAL, "check blocks per CU must be 1..16");
-            c->check_blocks_per_cu = (int)value;
-            return SDK_OK;
-        case SDK_OPT_WORK_COUNTER:
-            if (value != SDK_WORK_NODES && value != SDK_WORK_ROUNDS && value != SDK_WORK_DEPTH)
-                return fail(SDK_EINVAL, "bad work counter %lld", (long long)value);
-            c->work_rounds = (int)value;
-            return SDK_OK;
-        case SDK_OPT_DEVICE_CUS:
-            return fail(SDK_EINVAL, "SDK_OPT_DEVICE_CUS is read-only");
-        case SDK_OPT_TIMER_EVENTS:
-            return fail(SDK_EINVAL, "SDK_OPT_TIMER_EVENTS is read-only");
-        case SDK_OPT_TIMING:
-            if (value != 0 && value != 1) return fail(SDK_EINVAL, "timing must be 0 or 1");
-            c->timing = value != 0;
-            return SDK_OK;
-        case SDK_OPT_SOLVER:
-            if (value != SDK_SOLVER_WAVE && value != SDK_SOLVER_HALFWAVE && value != SDK_SOLVER_QUAD &&
-                value != SDK_SOLVER_LANE)
-                return fail(SDK_EINVAL, "bad solver %lld", (long long)value);
-            c->solver = (int)value;
-            return SDK_OK;
-        case SDK_OPT_WAVES_PER_CU2:
-            if (value < 1 || value > 32) return fail(SDK_EINVAL, "waves per CU must be 1..32");
-            c->waves_per_cu2 = (int)value;
-            return SDK_OK;
-        case SDK_OPT_SOLVE_CHUNK:
-            if (value < 0 || value > 4096) return fail(SDK_EINVAL, "solve chunk must be 0..4096");
-            c->solve_chunk = (int)value;
-            return SDK_OK;
-        case SDK_OPT_LOCKED:
-            if (value < 0 || value > 2) return fail(SDK_EINVAL, "locked must be 0, 1 or 2");
-            c->locked = (int)value;
-            return SDK_OK;
-        case SDK_OPT_DONATED:
-            return fail(SDK_EINVAL, "SDK_OPT_DONATED is read-only");
-        case SDK_OPT_SPLIT_BOARDS:
-            return fail(SDK_EINVAL, "SDK_OPT_SPLIT_BOARDS is read-only");
-        case SDK_OPT_RESUMED:
-            return fail(SDK_EINVAL, "SDK_OPT_RESUMED is read-only");
-        case SDK_OPT_LEX_BOARDS:
-            return fail(SDK_EINVAL, "SDK_OPT_LEX_BOARDS is read-only");
-        case SDK_OPT_DONATE_MAX:
-            if (value < 0) return fail(SDK_EINVAL, "SDK_OPT_DONATE_MAX must be >= 0");
-            c->dn_max = value;
-            return SDK_OK;
-        case SDK_OPT_DN_FAULT:
-            if (value != 0 && value != 1) return fail(SDK_EINVAL, "SDK_OPT_DN_FAULT must be 0 or 1");
-            c->dn_fault = (int)value;
-            return SDK_OK;
-        case SDK_OPT_DONATE_HELPERS:
-            if (value < 1 || value > 4096) return fail(SDK_EINVAL, "SDK_OPT_DONATE_HELPERS must be 1..4096");
-            c->dn_helpers = (int)value;
-            return SDK_OK;
-        case SDK_OPT_DONATE_RESUME:
-            if (value != 0 && value != 1) return fail(SDK_EINVAL, "SDK_OPT_DONATE_RESUME must be 0 or 1");
-            c->dn_resume = (int)value;
-            return SDK_OK;
-        case SDK_OPT_DONATE_MODE:
-            if (value != 0 && value != 1) return fail(SDK_EINVAL, "donate mode must be 0 (LEX) or 1 (exhaustive)");
-            c->dn_exhaustive = (int)value;
-            return SDK_OK;
-        case SDK_OPT_DONATE:
-            if (value < 0 || value > (1 << 30)) return fail(SDK_EINVAL, "donate must be 0, 1 or a split budget >= 2");
-            c->donate = (int)value;
-            return SDK_OK;
-        case SDK_OPT_PROP32:
-            if (value != 0 && value != 1) return fail(SDK_EINVAL, "SDK_OPT_PROP32 is 0 or 1");
-            c->prop32 = (int)value;
-            return SDK_OK;
-        case SDK_OPT_PROP32_LC:
-            if (value < 0 || (value & 0xFF) < 1 || (value & 0xFF) > 64 || (value >> 8) > 64)
-                return fail(SDK_EINVAL, "SDK_OPT_PROP32_LC: period 1..64 | first step 0..64 << 8");
-            c->prop32_lc = (int)value;
-            return SDK_OK;
-        case SDK_OPT_PROP32_MIN:
-            if (value < 1) return fail(SDK_EINVAL, "SDK_OPT_PROP32_MIN must be >= 1");
-            c->prop32_min = value;
-            return SDK_OK;
-        case SDK_OPT_PROP32_HANDOVER:
-            if (value != 0 && value != 1) return fail(SDK_EINVAL, "SDK_OPT_PROP32_HANDOVER is 0 or 1");
-            c->prop32_handover = (int)value;
-            return SDK_OK;
-        case SDK_OPT_PROP32_TAIL:
-            if (value < 0 || (value & 0xFF) > 64 || (value >> 8) > 96) return fail(SDK_EINVAL, "SDK_OPT_PROP32_TAIL out of range");
-            c->prop32_tail_live = (int)(value & 0xFF);
-            c->prop32_tail_step = (int)(value >> 8);
-            return SDK_OK;
-        case SDK_OPT_XCD_HEADS:
-            if (value != 0 && value != 1) return fail(SDK_EINVAL, "xcd heads must be 0 or 1");
-            c->xcd_heads = (int)value;
-            return SDK_OK;
-        case SDK_OPT_GEN_CAP:
-            if (value < 81 || value > 0x7FFFFFFFll) return fail(SDK_EINVAL, "SDK_OPT_GEN_CAP must be 81..2^31-1");
-            c->gen_cap = value;
-            return SDK_OK;
-        case SDK_OPT_CHECK_VARIANT:
-            if (value < SDK_CHECK_REG1 || value > SDK_CHECK_WAVE2) return fail(SDK_EINVAL, "bad check variant %lld", (long long)value);
-            c->check_variant = (int)value;
-            return SDK_OK;
-        default:
-            return fail(SDK_EINVAL, "unknown option %d", key);
-    }
-}
-
 // diagnostics (not in the header): the donation control block of the last donating launch
 extern "C" int sdk_debug_dn_ctl(sdk_ctx* c, uint32_t* out16) {
     if (!c || !out16) return fail(SDK_EINVAL, "NULL argument");
@@ -1808,33 +1668,87 @@ int dn_check_error(sdk_ctx* c) {
                 "not valid", (err & sdk::kDnErrReg) ? "registration entry never written " : "",
                 (err & sdk::kDnErrLock) ? "record lock never released" : "");
 }
-}  // namespace
 
-int sdk_get_option(sdk_ctx* c, int key, int64_t* value) {
-    if (!c || !value) return fail(SDK_EINVAL, "NULL argument");
-    std::lock_guard<std::mutex> lk(c->mu);
+// The plain options: sdk_set_option stores a value in [lo, hi] in the context's field (else `msg`, which
+// may print the value with %lld), sdk_get_option reads it back.  (The helper functions below are static:
+// inside extern "C" the unnamed namespace alone does not keep their names out of the dynamic symbols.)
+struct OptionRow {
+    int key;
+    int64_t sdk_ctx::*field;
+    int64_t lo, hi;
+    const char* msg;
+};
+constexpr int64_t kAny = INT64_MAX;
+const OptionRow kOptions[] = {
+    {SDK_OPT_ORDER, &sdk_ctx::order, SDK_ORDER_MRV_UNIQUE, SDK_ORDER_LEX, "bad order %lld"},
+    {SDK_OPT_NODE_BUDGET, &sdk_ctx::budget, 0, kAny, "budget must be >= 0"},
+    {SDK_OPT_WAVES_PER_CU, &sdk_ctx::waves_per_cu, 1, 32, "waves per CU must be 1..32"},
+    {SDK_OPT_CHECK_BLOCKS_PER_CU, &sdk_ctx::check_blocks_per_cu, 1, 16, "check blocks per CU must be 1..16"},
+    {SDK_OPT_WORK_COUNTER, &sdk_ctx::work_rounds, SDK_WORK_NODES, SDK_WORK_DEPTH, "bad work counter %lld"},
+    {SDK_OPT_SOLVER, &sdk_ctx::solver, SDK_SOLVER_WAVE, SDK_SOLVER_LANE, "bad solver %lld"},
+    {SDK_OPT_WAVES_PER_CU2, &sdk_ctx::waves_per_cu2, 1, 32, "waves per CU must be 1..32"},
+    {SDK_OPT_CHECK_VARIANT, &sdk_ctx::check_variant, SDK_CHECK_REG1, SDK_CHECK_WAVE2, "bad check variant %lld"},
+    {SDK_OPT_SOLVE_CHUNK, &sdk_ctx::solve_chunk, 0, 4096, "solve chunk must be 0..4096"},
+    {SDK_OPT_TIMING, &sdk_ctx::timing, 0, 1, "timing must be 0 or 1"},
+    {SDK_OPT_LOCKED, &sdk_ctx::locked, 0, 2, "locked must be 0, 1 or 2"},
+    {SDK_OPT_XCD_HEADS, &sdk_ctx::xcd_heads, 0, 1, "xcd heads must be 0 or 1"},
+    {SDK_OPT_DONATE, &sdk_ctx::donate, 0, 1 << 30, "donate must be 0, 1 or a split budget >= 2"},
+    {SDK_OPT_DONATE_MODE, &sdk_ctx::dn_exhaustive, 0, 1, "donate mode must be 0 (LEX) or 1 (exhaustive)"},
+    {SDK_OPT_DONATE_MAX, &sdk_ctx::dn_max, 0, kAny, "SDK_OPT_DONATE_MAX must be >= 0"},
+    {SDK_OPT_DN_FAULT, &sdk_ctx::dn_fault, 0, 1, "SDK_OPT_DN_FAULT must be 0 or 1"},
+    {SDK_OPT_DONATE_HELPERS, &sdk_ctx::dn_helpers, 1, 4096, "SDK_OPT_DONATE_HELPERS must be 1..4096"},
+    {SDK_OPT_DONATE_RESUME, &sdk_ctx::dn_resume, 0, 1, "SDK_OPT_DONATE_RESUME must be 0 or 1"},
+    {SDK_OPT_PROP32, &sdk_ctx::prop32, 0, 1, "SDK_OPT_PROP32 is 0 or 1"},
+    {SDK_OPT_PROP32_MIN, &sdk_ctx::prop32_min, 1, kAny, "SDK_OPT_PROP32_MIN must be >= 1"},
+    {SDK_OPT_PROP32_HANDOVER, &sdk_ctx::prop32_handover, 0, 1, "SDK_OPT_PROP32_HANDOVER is 0 or 1"},
+    {SDK_OPT_GEN_CAP, &sdk_ctx::gen_cap, 81, 0x7FFFFFFFll, "SDK_OPT_GEN_CAP must be 81..2^31-1"},
+};
+static const OptionRow* option_row(int key) {
+    for (const OptionRow& r : kOptions)
+        if (r.key == key) return &r;
+    return nullptr;
+}
+
+// The packed options: several small fields in one value.
+static bool packed_option(int key) { return key == SDK_OPT_PROP32_LC || key == SDK_OPT_PROP32_TAIL; }
+static int set_packed_option(sdk_ctx* c, int key, int64_t value) {
+    if (key == SDK_OPT_PROP32_LC) {
+        if (value < 0 || (value & 0xFF) < 1 || (value & 0xFF) > 64 || (value >> 8) > 64)
+            return fail(SDK_EINVAL, "SDK_OPT_PROP32_LC: period 1..64 | first step 0..64 << 8");
+        c->prop32_lc = value;
+    } else {   // SDK_OPT_PROP32_TAIL
+        if (value < 0 || (value & 0xFF) > 64 || (value >> 8) > 96) return fail(SDK_EINVAL, "SDK_OPT_PROP32_TAIL out of range");
+        c->prop32_tail_live = value & 0xFF;
+        c->prop32_tail_step = value >> 8;
+    }
+    return SDK_OK;
+}
+static int64_t get_packed_option(const sdk_ctx* c, int key) {
+    return key == SDK_OPT_PROP32_LC ? c->prop32_lc : (c->prop32_tail_live | (c->prop32_tail_step << 8));
+}
+
+// The read-only options: their names (nullptr: not one of them) and their values, most of them read
+// from device memory after waiting for the last solve on the context's stream.
+static const char* read_only_option(int key) {
     switch (key) {
-        case SDK_OPT_ORDER: *value = c->order; return SDK_OK;
-        case SDK_OPT_NODE_BUDGET: *value = (int64_t)c->budget; return SDK_OK;
-        case SDK_OPT_WAVES_PER_CU: *value = c->waves_per_cu; return SDK_OK;
-        case SDK_OPT_CHECK_BLOCKS_PER_CU: *value = c->check_blocks_per_cu; return SDK_OK;
-        case SDK_OPT_WORK_COUNTER: *value = c->work_rounds; return SDK_OK;
+        case SDK_OPT_DEVICE_CUS: return "SDK_OPT_DEVICE_CUS";
+        case SDK_OPT_TIMER_EVENTS: return "SDK_OPT_TIMER_EVENTS";
+        case SDK_OPT_DONATED: return "SDK_OPT_DONATED";
+        case SDK_OPT_SPLIT_BOARDS: return "SDK_OPT_SPLIT_BOARDS";
+        case SDK_OPT_LEX_BOARDS: return "SDK_OPT_LEX_BOARDS";
+        case SDK_OPT_RESUMED: return "SDK_OPT_RESUMED";
+        case SDK_OPT_PROP32_UNDECIDED: return "SDK_OPT_PROP32_UNDECIDED";
+        default: return nullptr;
+    }
+}
+static int get_read_only_option(sdk_ctx* c, int key, int64_t* value) {
+    *value = 0;
+    switch (key) {
         case SDK_OPT_DEVICE_CUS: *value = c->cus; return SDK_OK;
-        case SDK_OPT_SOLVER: *value = c->solver; return SDK_OK;
-        case SDK_OPT_WAVES_PER_CU2: *value = c->waves_per_cu2; return SDK_OK;
-        case SDK_OPT_CHECK_VARIANT: *value = c->check_variant; return SDK_OK;
-        case SDK_OPT_SOLVE_CHUNK: *value = c->solve_chunk; return SDK_OK;
-        case SDK_OPT_TIMING: *value = c->timing ? 1 : 0; return SDK_OK;
-        case SDK_OPT_LOCKED: *value = c->locked; return SDK_OK;
-        case SDK_OPT_XCD_HEADS: *value = c->xcd_heads; return SDK_OK;
-        case SDK_OPT_PROP32: *value = c->prop32; return SDK_OK;
-        case SDK_OPT_PROP32_LC: *value = c->prop32_lc; return SDK_OK;
-        case SDK_OPT_PROP32_MIN: *value = c->prop32_min; return SDK_OK;
-        case SDK_OPT_GEN_CAP: *value = c->gen_cap; return SDK_OK;
-        case SDK_OPT_PROP32_HANDOVER: *value = c->prop32_handover; return SDK_OK;
-        case SDK_OPT_PROP32_TAIL: *value = c->prop32_tail_live | (c->prop32_tail_step << 8); return SDK_OK;
+        case SDK_OPT_TIMER_EVENTS: *value = (int64_t)c->events.size(); return SDK_OK;
+        case SDK_OPT_SPLIT_BOARDS: return read_dn_stat(c, 0, value);
+        case SDK_OPT_LEX_BOARDS: return read_dn_stat(c, 1, value);
         case SDK_OPT_PROP32_UNDECIDED: {
-            *value = 0;
             if (!c->prop32_ran) return SDK_OK;
             HIPCALL(hipSetDevice(c->device));
             uint32_t v = 0;
@@ -1843,18 +1757,9 @@ int sdk_get_option(sdk_ctx* c, int key, int64_t* value) {
             *value = v;
             return SDK_OK;
         }
-        case SDK_OPT_DONATE: *value = c->donate; return SDK_OK;
-        case SDK_OPT_SPLIT_BOARDS: return read_dn_stat(c, 0, value);
-        case SDK_OPT_DONATE_MODE: *value = c->dn_exhaustive; return SDK_OK;
-        case SDK_OPT_LEX_BOARDS: return read_dn_stat(c, 1, value);
-        case SDK_OPT_DONATE_MAX: *value = c->dn_max; return SDK_OK;
-        case SDK_OPT_DN_FAULT: *value = c->dn_fault; return SDK_OK;
-        case SDK_OPT_DONATE_HELPERS: *value = c->dn_helpers; return SDK_OK;
-        case SDK_OPT_DONATE_RESUME: *value = c->dn_resume; return SDK_OK;
         case SDK_OPT_DONATED: {
             // items handed out by the last phased solve's donation launches (of its last
             // kDnCapBoards-board pass; waits for it on the context's stream)
-            *value = 0;
             if (!c->dn.p || c->dn_epoch == 0 || !c->dn_ran) return SDK_OK;
             HIPCALL(hipSetDevice(c->device));
             sdk::DnCtl h[2];
@@ -1865,9 +1770,8 @@ int sdk_get_option(sdk_ctx* c, int key, int64_t* value) {
             *value = (int64_t)h[0].delivered + (int64_t)h[1].delivered;
             return SDK_OK;
         }
-        case SDK_OPT_RESUMED: {
+        default: {   // SDK_OPT_RESUMED
             // boards the last phased solve resumed (donation area 0; waits for the solve)
-            *value = 0;
             if (!c->dn.p || c->dn_epoch == 0 || !c->dn_ran) return SDK_OK;
             HIPCALL(hipSetDevice(c->device));
             sdk::DnSeed h;
@@ -1877,9 +1781,36 @@ int sdk_get_option(sdk_ctx* c, int key, int64_t* value) {
             *value = (int64_t)h.boards;
             return SDK_OK;
         }
-        case SDK_OPT_TIMER_EVENTS: *value = (int64_t)c->events.size(); return SDK_OK;
-        default: return fail(SDK_EINVAL, "unknown option %d", key);
     }
+}
+}  // namespace
+
+int sdk_set_option(sdk_ctx* c, int key, int64_t value) {
+    if (!c) return fail(SDK_EINVAL, "ctx is NULL");
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (const OptionRow* r = option_row(key)) {
+        if (value < r->lo || value > r->hi) return fail(SDK_EINVAL, r->msg, (long long)value);
+        c->*(r->field) = value;
+        return SDK_OK;
+    }
+    if (packed_option(key)) return set_packed_option(c, key, value);
+    if (const char* name = read_only_option(key)) return fail(SDK_EINVAL, "%s is read-only", name);
+    return fail(SDK_EINVAL, "unknown option %d", key);
+}
+
+int sdk_get_option(sdk_ctx* c, int key, int64_t* value) {
+    if (!c || !value) return fail(SDK_EINVAL, "NULL argument");
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (const OptionRow* r = option_row(key)) {
+        *value = c->*(r->field);
+        return SDK_OK;
+    }
+    if (packed_option(key)) {
+        *value = get_packed_option(c, key);
+        return SDK_OK;
+    }
+    if (read_only_option(key)) return get_read_only_option(c, key, value);
+    return fail(SDK_EINVAL, "unknown option %d", key);
 }
 
 int sdk_dev_alloc(sdk_ctx* c, size_t bytes, void** dptr) {

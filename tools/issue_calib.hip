@@ -27,7 +27,6 @@
 #include <cstdlib>
 #include <cstring>
 
-#define SDK_NO_SOLVE_KERNEL
 #include "../distributed_sudoku_solver_amd/csrc/solve4_kernel.h"
 
 #define CK(x) do { hipError_t e = (x); if (e != hipSuccess) { \
