@@ -77,7 +77,7 @@ __global__ void g32_verdict_kernel(const uint32_t* list, const int8_t* sub_st, u
 
 // the lane's half of a 64-bit board mask
 __device__ __forceinline__ uint32_t g32_word(const P32Lane& w, uint64_t m) {
-    return w.half ? (uint32_t)(m >> 32) : (uint32_t)m;
+    return w.half() ? (uint32_t)(m >> 32) : (uint32_t)m;
 }
 
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) void grade32_kernel(Grade32Args ga) {
@@ -153,17 +153,18 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) void gr
             __builtin_amdgcn_wave_barrier();
             if (handed) stuck &= ~p32_refute_handed(w, lds, G, handed);
             // this lane as board (half, hl): the clear bits hl of its half's 81 single words
-            const uint32_t bit = p32_opq(w.hl);
+            const uint32_t bit = w.hl();
+            const p32_lds_t* const reg = w.reg();
 #pragma unroll 9
             for (uint32_t j = 0; j < 81u; ++j) {
                 const uint32_t s =
-                    *(const volatile __attribute__((address_space(3))) uint32_t*)(w.reg + kP32Rec * j + 36u);
+                    *(const volatile __attribute__((address_space(3))) uint32_t*)(reg + kP32Rec * j + 36u);
                 nopen += (~s >> bit) & 1u;
             }
             __builtin_amdgcn_wave_barrier();
         }
         // the grades; then the answers, the statuses and the list
-        const uint32_t me = p32_opq(threadIdx.x);        // board me of the group (32 half + hl)
+        const uint32_t me = p32_tid();        // board me of the group (32 half + hl)
         if ((G.valid >> me) & 1ull) {
             const bool sv = (G.solved >> me) & 1ull, st = (stuck >> me) & 1ull;
             ga.level[G.base + me] =

@@ -59,10 +59,13 @@ constexpr uint32_t kP32Rec = 40;         // bytes per cell record: 9 candidate w
 constexpr uint32_t kP32URec = 72;        // bytes per unit record: (T_d, twos_d), d = 0..8
 constexpr uint32_t kP32TRec = 40;        // bytes per triad record: 9 words + pad
 constexpr uint32_t kP32ColTri = 1280;    // the column triads' records (32 row-triad slots before)
-constexpr uint32_t kP32Region = 3456;    // bytes per half: 81 cell records + the spare lanes' record 81
+constexpr uint32_t kP32Region = 3456;    // bytes per half: 81 cell records + the spare lanes' records 81..83
                                          // (= 32 boards x 108 B of the answers' staging, p32_stage_byte)
-constexpr uint32_t kP32Table = 2 * kP32Region;   // p32_unit's read order, 40 B per lane (p32_order_table)
-constexpr uint32_t kP32Lds = kP32Table + 64 * 40;
+constexpr uint32_t kP32Table = 2 * kP32Region;   // p32_unit's read order, one table for both halves
+constexpr uint32_t kP32TabRec = 8;               // ... bytes per unit lane: nine 7-bit cell indices
+constexpr uint32_t kP32Lds = kP32Table + 32 * kP32TabRec;
+// 20 workgroups per CU (160 KiB of LDS), five waves per SIMD
+static_assert(kP32Lds <= 8192u, "prop32: LDS per workgroup above a twentieth of the CU's");
 
 // OR / AND over the 32 lanes of each half, result in every lane of the half: rotations inside
 // each row of 16 (DPP), then the two rows of each half combined -- v_permlane16_swap (gfx950: the
@@ -100,22 +103,18 @@ __device__ __forceinline__ uint2 p32_ld(p32_lds_t* base, uint32_t off) {
     const uint64_t v = *(const volatile __attribute__((address_space(3))) uint64_t*)(base + off);
     return make_uint2((uint32_t)v, (uint32_t)(v >> 32));
 }
-__device__ __forceinline__ uint2 p32_lda(uint32_t addr) {   // an absolute LDS address
-    const uint64_t v = *(const volatile __attribute__((address_space(3))) uint64_t*)(uintptr_t)addr;
-    return make_uint2((uint32_t)v, (uint32_t)(v >> 32));
-}
 // stores volatile too: merged pairs become ds_write2_b64, 13 cycles against 2 x 6 (same table)
-// The unit phase's per-lane read-order table (p32_order_table) keeps the nine record addresses as
-// 16-bit halves (three ds_read_b64 per step, halves split by VOP2 shifts and masks) instead of
-// 32-bit words (five reads) -- two LDS instructions fewer per step on the pipe that bounds the
-// kernel, for nine pairing VALU ops
+// The unit phase's per-lane read-order table (p32_order_table) keeps the unit's nine cells as 7-bit
+// cell indices in one 64-bit word per unit lane: one ds_read_b64 per step (the 16-bit addresses it
+// replaces took three, 32-bit ones five) on the pipe that bounds the kernel.  An index is relative
+// to the half's region, so both halves share one table (256 B instead of 2,560: what lets a fifth
+// workgroup per SIMD fit in the CU's LDS); a record's address is one multiply-add on the field.
 __device__ __forceinline__ uint64_t p32_tab64(const p32_lds_t* lds, uint32_t off) {
     return *(const volatile __attribute__((address_space(3))) uint64_t*)(lds + off);
 }
-// 16-bit field k (0..3) of a table word
+// the offset, in the half's region, of the cell record named by field k (0..8) of a table word
 __device__ __forceinline__ uint32_t p32_tab_field(uint64_t v, int k) {
-    const uint32_t w = k < 2 ? (uint32_t)v : (uint32_t)(v >> 32);
-    return (k & 1) ? w >> 16 : w & 0xFFFFu;
+    return __umul24((uint32_t)(v >> (7 * k)) & 127u, kP32Rec);
 }
 __device__ __forceinline__ void p32_st(p32_lds_t* base, uint32_t off, uint32_t x, uint32_t y) {
     *(volatile __attribute__((address_space(3))) uint64_t*)(base + off) = (uint64_t)x | ((uint64_t)y << 32);
@@ -129,10 +128,36 @@ __device__ __forceinline__ uint32_t p32_opq(uint32_t v) {
     return v;
 }
 
+// The lane's place in its half.  Kept through the step loop: `act` (a lane mask, in scalar registers)
+// and one packed word, `pk`; everything else is derived where it is used, through opaque copies, so
+// no derived address is parked in a register of its own across the loop (at 96 registers each one
+// parked is one spilled).
+// The thread index (one wave per workgroup: the lane's index in its wave) from the exec-mask count,
+// two VALU ops where it is used: the launch's own copy in v0 would be one more register held
+// through the step loop.
+__device__ __forceinline__ uint32_t p32_tid() {
+    uint32_t t;
+    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(t));
+    return t;
+}
+
 struct P32Lane {
-    uint32_t half, hl;
-    bool act;
-    p32_lds_t* reg;        // the half's LDS region
+    bool act;              // hl < 27: a real lane (row triad hl, unit hl)
+    p32_lds_t* lds;
+    __device__ __forceinline__ uint32_t tid() const { return p32_tid(); }
+    // (opaque: with its range known the compiler divides it in 16-bit SDWA operations, whose constant
+    // operands sit in registers through the loop)
+    __device__ __forceinline__ uint32_t hl() const { return p32_opq(tid() & 31u); }
+    __device__ __forceinline__ uint32_t half() const { return tid() >> 5; }
+    __device__ __forceinline__ p32_lds_t* reg() const { return lds + __umul24(half(), kP32Region); }   // the half's LDS region
+    // both for the step's phases, from the one word that is kept through the loop (two VALU ops a
+    // phase, where the thread index would take five)
+    uint32_t pk;           // hl | the region's offset << 16
+    __device__ __forceinline__ void place(uint32_t& hl_, p32_lds_t*& reg_) const {
+        const uint32_t t = p32_opq(pk);
+        hl_ = p32_opq(t & 0xFFFFu);
+        reg_ = lds + p32_opq(t >> 16);   // (opaque: one add per address, not a multiply-add)
+    }
 };
 
 struct P32Cells {
@@ -167,17 +192,23 @@ __device__ __forceinline__ void p32_singles(const P32Lane& w, P32Cells& x, uint3
         empty |= ~o;
         alls &= x.s[k];
     }
-    // spare lanes store into record 81 (no branch: a divergent region inside the step loop cost the
-    // cell words a second register home); their unit reads return whatever is there
-    const uint32_t rec = kP32Rec * p32_opq(w.hl);
+    // spare lanes store as triad 27, into records 81..83 (inside the region, past every record that is
+    // read; no branch: a divergent region inside the step loop cost the cell words a second register
+    // home, and no select against a constant offset: that constant would sit in a register through
+    // the loop); their unit reads return whatever is there
+    static_assert(kP32Rec * 84u <= kP32Region, "the spare lanes' records lie inside the region");
+    uint32_t hl;
+    p32_lds_t* reg;
+    w.place(hl, reg);
+    reg += __umul24(min(hl, 27u), 3u * kP32Rec);
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
-        const uint32_t o = w.act ? 3u * rec + kP32Rec * k : 81u * kP32Rec;
-        p32_st(w.reg, o, x.c[k][0], x.c[k][1]);
-        p32_st(w.reg, o + 8, x.c[k][2], x.c[k][3]);
-        p32_st(w.reg, o + 16, x.c[k][4], x.c[k][5]);
-        p32_st(w.reg, o + 24, x.c[k][6], x.c[k][7]);
-        p32_st(w.reg, o + 32, x.c[k][8], x.s[k]);
+        const uint32_t o = kP32Rec * k;
+        p32_st(reg, o, x.c[k][0], x.c[k][1]);
+        p32_st(reg, o + 8, x.c[k][2], x.c[k][3]);
+        p32_st(reg, o + 16, x.c[k][4], x.c[k][5]);
+        p32_st(reg, o + 24, x.c[k][6], x.c[k][7]);
+        p32_st(reg, o + 32, x.c[k][8], x.s[k]);
     }
 }
 
@@ -209,26 +240,44 @@ __device__ __forceinline__ void p32_unit2(uint32_t& ones, uint32_t& twos, uint32
 }
 // cell update, first pass for digit d:  U = cT|rT|bT, H = ~(cW & rW & bW) (0x7F; W = twos: a candidate of
 // the cell outside some unit's twos is that unit's hidden single), c &= ~U | s (0xB0: S0 & (~S1 | S2)),
-// anyh |= c & H (0xF8); with CHG, chg |= c_old & ~c_new (0xF4: S0 | S1 & ~S2)
-template <bool CHG>
+// anyh |= c & H (0xF8); with CHG, chg |= c_old & ~c_new (0xF4: S0 | S1 & ~S2).  FIRST (a cell's first
+// digit): anyh = c & H, so no zeroed register enters
+template <bool CHG, bool FIRST = false>
 __device__ __forceinline__ void p32_upd1(uint32_t& c, uint32_t& H, uint32_t& anyh, uint32_t& chg, uint32_t s,
                                          uint32_t cT, uint32_t rT, uint32_t bT, uint32_t cH, uint32_t rH, uint32_t bH) {
-    uint32_t U, v;
-    if (CHG)
-        asm(SDK_OR3("%[u]", "%[ct]", "%[rt]", "%[bt]")
+    uint32_t v;   // (U in v's register: one temporary, not two)
+    if (FIRST && CHG)
+        asm(SDK_OR3("%[v]", "%[ct]", "%[rt]", "%[bt]")
             "v_bitop3_b32 %[h], %[ch], %[rh], %[bh] bitop3:0x7f\n\t"
-            "v_bitop3_b32 %[v], %[c], %[u], %[s] bitop3:0xb0\n\t"
+            "v_bitop3_b32 %[v], %[c], %[v], %[s] bitop3:0xb0\n\t"
+            "v_bitop3_b32 %[g], %[g], %[c], %[v] bitop3:0xf4\n\t"
+            "v_and_b32 %[a], %[v], %[h]"
+            : [h] "=&v"(H), [v] "=&v"(v), [g] "+v"(chg), [a] "=&v"(anyh)
+            : [c] "v"(c), [s] "v"(s), [ct] "v"(cT), [rt] "v"(rT), [bt] "v"(bT), [ch] "v"(cH), [rh] "v"(rH),
+              [bh] "v"(bH));
+    else if (FIRST)
+        asm(SDK_OR3("%[v]", "%[ct]", "%[rt]", "%[bt]")
+            "v_bitop3_b32 %[h], %[ch], %[rh], %[bh] bitop3:0x7f\n\t"
+            "v_bitop3_b32 %[v], %[c], %[v], %[s] bitop3:0xb0\n\t"
+            "v_and_b32 %[a], %[v], %[h]"
+            : [h] "=&v"(H), [v] "=&v"(v), [a] "=&v"(anyh)
+            : [c] "v"(c), [s] "v"(s), [ct] "v"(cT), [rt] "v"(rT), [bt] "v"(bT), [ch] "v"(cH), [rh] "v"(rH),
+              [bh] "v"(bH));
+    else if (CHG)
+        asm(SDK_OR3("%[v]", "%[ct]", "%[rt]", "%[bt]")
+            "v_bitop3_b32 %[h], %[ch], %[rh], %[bh] bitop3:0x7f\n\t"
+            "v_bitop3_b32 %[v], %[c], %[v], %[s] bitop3:0xb0\n\t"
             "v_bitop3_b32 %[g], %[g], %[c], %[v] bitop3:0xf4\n\t"
             "v_bitop3_b32 %[a], %[a], %[v], %[h] bitop3:0xf8"
-            : [u] "=&v"(U), [h] "=&v"(H), [v] "=&v"(v), [g] "+v"(chg), [a] "+v"(anyh)
+            : [h] "=&v"(H), [v] "=&v"(v), [g] "+v"(chg), [a] "+v"(anyh)
             : [c] "v"(c), [s] "v"(s), [ct] "v"(cT), [rt] "v"(rT), [bt] "v"(bT), [ch] "v"(cH), [rh] "v"(rH),
               [bh] "v"(bH));
     else
-        asm(SDK_OR3("%[u]", "%[ct]", "%[rt]", "%[bt]")
+        asm(SDK_OR3("%[v]", "%[ct]", "%[rt]", "%[bt]")
             "v_bitop3_b32 %[h], %[ch], %[rh], %[bh] bitop3:0x7f\n\t"
-            "v_bitop3_b32 %[v], %[c], %[u], %[s] bitop3:0xb0\n\t"
+            "v_bitop3_b32 %[v], %[c], %[v], %[s] bitop3:0xb0\n\t"
             "v_bitop3_b32 %[a], %[a], %[v], %[h] bitop3:0xf8"
-            : [u] "=&v"(U), [h] "=&v"(H), [v] "=&v"(v), [a] "+v"(anyh)
+            : [h] "=&v"(H), [v] "=&v"(v), [a] "+v"(anyh)
             : [c] "v"(c), [s] "v"(s), [ct] "v"(cT), [rt] "v"(rT), [bt] "v"(bT), [ch] "v"(cH), [rh] "v"(rH),
               [bh] "v"(bH));
     c = v;
@@ -264,15 +313,16 @@ __device__ __forceinline__ void p32_unit_cells(uint32_t j, uint32_t& u0, uint32_
 // the givens); such a board is not exact and goes to the search
 __device__ __forceinline__ uint32_t p32_dups(const P32Lane& w, const p32_lds_t* lds) {
     // the unit's cells from p32_unit's order table (any order will do; no lane-dependent branch)
-    const uint32_t tb = kP32Table + 40u * p32_opq(threadIdx.x);
+    const uint32_t tb = kP32Table + kP32TabRec * w.hl();
+    p32_lds_t* const reg = w.reg();
     uint32_t T[9], dup = 0u;
     uint64_t tw = 0ull;
 #pragma unroll
     for (int q = 0; q < 9; ++q) {
-        if (q % 4 == 0) tw = p32_tab64(lds, tb + 2u * q);
-        const uint32_t o = p32_tab_field(tw, q % 4);
-        const uint2 r0 = p32_lda(o), r1 = p32_lda(o + 8), r2 = p32_lda(o + 16), r3 = p32_lda(o + 24),
-                    r4 = p32_lda(o + 32);
+        if (q == 0) tw = p32_tab64(lds, tb);
+        const uint32_t o = p32_tab_field(tw, q);
+        const uint2 r0 = p32_ld(reg, o), r1 = p32_ld(reg, o + 8), r2 = p32_ld(reg, o + 16),
+                    r3 = p32_ld(reg, o + 24), r4 = p32_ld(reg, o + 32);
         const uint32_t a[9] = {r0.x, r0.y, r1.x, r1.y, r2.x, r2.y, r3.x, r3.y, r4.x};
 #pragma unroll
         for (int d = 0; d < 9; ++d) {
@@ -300,17 +350,19 @@ __device__ __forceinline__ uint32_t p32_dups(const P32Lane& w, const p32_lds_t* 
 // so that those nine cells' records (40 B apart) fall in nine different bank pairs (cell index mod 32
 // distinct in every digit class; found by a search over relabelled and permuted pattern grids).  The
 // natural order met two addresses per bank pair on every read (15-16 % of the launch's LDS cycles
-// were bank conflicts).  The per-lane offsets are a table in LDS (40 B per lane; 16-bit entries, above).
+// were bank conflicts).  The per-lane order is a table in LDS (one word per unit lane, above).
 // kDups (a group's first step): also the digits given twice in the unit (p32_dups) from the same
 // loaded records -- a digit closed in at least two of the unit's cells: the majority of three closed
 // terms over the first three cells, then of (closed so far, the pair's two closed terms) -- instead of
 // a second pass over the nine records
 template <bool kDups>
 __device__ __forceinline__ void p32_unit(const P32Lane& w, const p32_lds_t* lds, uint32_t& miss, uint32_t& dup) {
-    const uint32_t j = p32_opq(w.hl);   // the unit record written below
-    const uint32_t tb = kP32Table + 40u * p32_opq(threadIdx.x);
+    uint32_t j;   // the unit record written below
+    p32_lds_t* reg;
+    w.place(j, reg);
+    const uint32_t tb = kP32Table + kP32TabRec * j;
     uint32_t ones[9], twos[9], T[9];
-    uint64_t tA, tB = 0ull;   // table words: steps 0-3, 4-7 (step 8: its own read)
+    uint64_t tA;   // the table word
     // cells 0, 1, 2
     {
         uint32_t a[3][9], s[3];
@@ -318,8 +370,8 @@ __device__ __forceinline__ void p32_unit(const P32Lane& w, const p32_lds_t* lds,
 #pragma unroll
         for (int q = 0; q < 3; ++q) {
             const uint32_t o = p32_tab_field(tA, q);
-            const uint2 r0 = p32_lda(o), r1 = p32_lda(o + 8), r2 = p32_lda(o + 16), r3 = p32_lda(o + 24),
-                        r4 = p32_lda(o + 32);
+            const uint2 r0 = p32_ld(reg, o), r1 = p32_ld(reg, o + 8), r2 = p32_ld(reg, o + 16),
+                        r3 = p32_ld(reg, o + 24), r4 = p32_ld(reg, o + 32);
             a[q][0] = r0.x; a[q][1] = r0.y; a[q][2] = r1.x; a[q][3] = r1.y; a[q][4] = r2.x;
             a[q][5] = r2.y; a[q][6] = r3.x; a[q][7] = r3.y; a[q][8] = r4.x;
             s[q] = r4.y;
@@ -341,32 +393,33 @@ __device__ __forceinline__ void p32_unit(const P32Lane& w, const p32_lds_t* lds,
                      "+v"(T[0]), "+v"(T[1]), "+v"(T[2]), "+v"(T[3]), "+v"(T[4]), "+v"(T[5]), "+v"(T[6]),
                      "+v"(T[7]), "+v"(T[8])::"memory");
         uint32_t a[2][9], s[2];
-        // steps 3 + 2p, 4 + 2p: (3, 4) from words A and B, (5, 6) from B, (7, 8) from B and C
+        // steps 3 + 2p, 4 + 2p
         uint32_t oo[2];
-        if (p == 0) {
-            tB = p32_tab64(lds, tb + 8u);
-            oo[0] = p32_tab_field(tA, 3);
-            oo[1] = p32_tab_field(tB, 0);
-        } else if (p == 1) {
-            oo[0] = p32_tab_field(tB, 1);
-            oo[1] = p32_tab_field(tB, 2);
-        } else {
-            oo[0] = p32_tab_field(tB, 3);
-            oo[1] = p32_tab_field(p32_tab64(lds, tb + 16u), 0);
-        }
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const uint32_t o = oo[h];
-            const uint2 r0 = p32_lda(o), r1 = p32_lda(o + 8), r2 = p32_lda(o + 16), r3 = p32_lda(o + 24),
-                        r4 = p32_lda(o + 32);
-            a[h][0] = r0.x; a[h][1] = r0.y; a[h][2] = r1.x; a[h][3] = r1.y; a[h][4] = r2.x;
-            a[h][5] = r2.y; a[h][6] = r3.x; a[h][7] = r3.y; a[h][8] = r4.x;
-            s[h] = r4.y;
-        }
+        oo[0] = p32_tab_field(tA, 3 + 2 * p);
+        oo[1] = p32_tab_field(tA, 4 + 2 * p);
+        // the last words first (they hold s), then the digits' words two ahead of their use: 12
+        // registers of the pair's 20 in flight at a time
+        auto rd = [&](int i) {
+            const uint2 u = p32_ld(reg, oo[0] + 8 * i), v = p32_ld(reg, oo[1] + 8 * i);
+            a[0][2 * i] = u.x;
+            a[1][2 * i] = v.x;
+            if (i < 4) {
+                a[0][2 * i + 1] = u.y;
+                a[1][2 * i + 1] = v.y;
+            } else {
+                s[0] = u.y;
+                s[1] = v.y;
+            }
+        };
+        rd(4);
+        rd(0);
+        rd(1);
 #pragma unroll
         for (int d = 0; d < 9; ++d) {
-            if (kDups) dup |= p32_b3<0xE8u>(T[d], a[0][d] & s[0], a[1][d] & s[1]);   // T: closed so far
-            p32_unit2(ones[d], twos[d], T[d], a[0][d], a[1][d], s[0], s[1]);
+            if (d % 2 == 0 && d / 2 + 2 < 4) rd(d / 2 + 2);
+            const int e = d == 0 ? 8 : d - 1;   // digit 8 (read with s) first
+            if (kDups) dup |= p32_b3<0xE8u>(T[e], a[0][e] & s[0], a[1][e] & s[1]);   // T: closed so far
+            p32_unit2(ones[e], twos[e], T[e], a[0][e], a[1][e], s[0], s[1]);
         }
     }
     // a digit with no cell: the complement of the and of the nine "in some cell" words (and3 chains)
@@ -382,48 +435,72 @@ __device__ __forceinline__ void p32_unit(const P32Lane& w, const p32_lds_t* lds,
     __builtin_amdgcn_wave_barrier();   // every lane's reads before the records are overwritten
     const uint32_t urec = kP32URec * j;   // spare lanes: unit slots 27..31
 #pragma unroll
-    for (int d = 0; d < 9; ++d) p32_st(w.reg, urec + 8 * d, T[d], twos[d]);
+    for (int d = 0; d < 9; ++d) p32_st(reg, urec + 8 * d, T[d], twos[d]);
 }
 
 // the cell update of one step; CHG: also returns the change bits of the lane's three cells (only the
 // step before a locked-candidates pass needs them: a board unchanged by it and by the pass is stuck).
-// The lane's cells 3j + k share row j / 3 and box 3 (j / 9) + j % 3: those two records are read once
-// (36 registers for the phase), each cell's column record beside its update.
+// The lane's cells 3j + k share row j / 3 and box 3 (j / 9) + j % 3.  Digit-major: per digit the row,
+// the box and the three columns' (T, twos) pairs -- five reads, 45 for the phase, each record read
+// once -- and the first pass for the digit's three cells; what waits for the second pass is H[k][d]
+// (27 words), not the row's and the box's 36 words beside nine H: the phase's peak is ~20 registers
+// lower, which is what lets the step run in 96.
 // GATE (the grading pass, grade32_kernel.h): the hidden-single restriction only for the boards of `hid`
 template <bool CHG, bool GATE = false>
 __device__ __forceinline__ uint32_t p32_cells(const P32Lane& w, P32Cells& x, uint32_t hid = ~0u) {
-    const uint32_t j = p32_opq(w.hl);
+    uint32_t j;
+    p32_lds_t* reg;
+    w.place(j, reg);
     const uint32_t r = j / 3, bc = j - 3 * r;          // row r, box column bc: columns 3 bc + k
-    const uint32_t rowrec = kP32URec * r, boxrec = kP32URec * (18 + 3 * (r / 3) + bc),
-                   colrec = kP32URec * (9 + 3 * bc);
-    uint32_t rT[9], rW[9], bT[9], bW[9];
+    // (24-bit multiplies: the 32-bit multiply-add is a 64-bit one, with a register pair for its result)
+    const uint32_t rowrec = __umul24(r, kP32URec), boxrec = __umul24(18 + 3 * (r / 3) + bc, kP32URec),
+                   colrec = __umul24(bc, 3 * kP32URec) + 9 * kP32URec;
+    uint32_t H[3][9], anyh[3], chg = 0u;
+    uint2 rw = p32_ld(reg, rowrec), c0 = p32_ld(reg, colrec), bx = p32_ld(reg, boxrec),
+          c1 = p32_ld(reg, colrec + kP32URec), c2 = p32_ld(reg, colrec + 2 * kP32URec);
+    // a cell's second pass, right after its last digit's first (its nine H words come free before the
+    // next cell's last digit)
+    auto second = [&](int k) {
+        if (GATE) anyh[k] &= hid;
+#pragma unroll
+        for (int d = 0; d < 9; ++d) p32_upd2<CHG>(x.c[k][d], H[k][d], anyh[k], chg);
+    };
 #pragma unroll
     for (int d = 0; d < 9; ++d) {
-        const uint2 v = p32_ld(w.reg, rowrec + 8 * d), u = p32_ld(w.reg, boxrec + 8 * d);
-        rT[d] = v.x;
-        rW[d] = v.y;
-        bT[d] = u.x;
-        bW[d] = u.y;
-    }
-    uint32_t chg = 0u;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        uint32_t H[9], anyh = 0u;
-#pragma unroll
-        for (int d = 0; d < 9; ++d) {
-            const uint2 c = p32_ld(w.reg, colrec + kP32URec * k + 8 * d);   // column 3 bc + k
-            p32_upd1<CHG>(x.c[k][d], H[d], anyh, chg, x.s[k], c.x, rT[d], bT[d], c.y, rW[d], bW[d]);
+        // the next digit's reads as this digit's registers come free: the row's and the box's pairs
+        // are the only ones in flight beside their predecessors (4 registers, not 10)
+        uint2 nrw = rw, nbx = bx;
+        (d == 0 ? p32_upd1<CHG, true> : p32_upd1<CHG, false>)(x.c[0][d], H[0][d], anyh[0], chg, x.s[0], c0.x, rw.x,
+                                                               bx.x, c0.y, rw.y, bx.y);
+        if (d < 8) {
+            nrw = p32_ld(reg, rowrec + 8 * (d + 1));
+            c0 = p32_ld(reg, colrec + 8 * (d + 1));
+        } else {
+            second(0);
         }
-        if (GATE) anyh &= hid;
-#pragma unroll
-        for (int d = 0; d < 9; ++d) p32_upd2<CHG>(x.c[k][d], H[d], anyh, chg);
+        (d == 0 ? p32_upd1<CHG, true> : p32_upd1<CHG, false>)(x.c[1][d], H[1][d], anyh[1], chg, x.s[1], c1.x, rw.x,
+                                                               bx.x, c1.y, rw.y, bx.y);
+        if (d < 8) {
+            nbx = p32_ld(reg, boxrec + 8 * (d + 1));
+            c1 = p32_ld(reg, colrec + kP32URec + 8 * (d + 1));
+        } else {
+            second(1);
+        }
+        (d == 0 ? p32_upd1<CHG, true> : p32_upd1<CHG, false>)(x.c[2][d], H[2][d], anyh[2], chg, x.s[2], c2.x, rw.x,
+                                                               bx.x, c2.y, rw.y, bx.y);
+        if (d < 8)
+            c2 = p32_ld(reg, colrec + 2 * kP32URec + 8 * (d + 1));
+        else
+            second(2);
+        rw = nrw;
+        bx = nbx;
     }
     return chg;
 }
 
 // the eliminations into the lane's triad (line tl, box index tb along the line) of one kind
 // (base: the row or column triads' records): lines L1, L2 of the band / stack, boxes B1, B2
-__device__ __forceinline__ void p32_elim(const P32Lane& w, uint32_t tl, uint32_t tb, uint32_t base,
+__device__ __forceinline__ void p32_elim(p32_lds_t* reg, uint32_t tl, uint32_t tb, uint32_t base,
                                          uint32_t (&e)[9]) {
     const uint32_t L0 = tl - tl % 3;
     const uint32_t L1 = L0 + (tl - L0 + 1) % 3, L2 = L0 + (tl - L0 + 2) % 3;
@@ -434,10 +511,10 @@ __device__ __forceinline__ void p32_elim(const P32Lane& w, uint32_t tl, uint32_t
                    oLB1 = base + kP32TRec * (3 * tl + B1), oLB2 = base + kP32TRec * (3 * tl + B2);
 #pragma unroll
     for (int h = 0; h < 5; ++h) {
-        const uint2 l1b = p32_ld(w.reg, oL1B + 8 * h), l1b1 = p32_ld(w.reg, oL1B1 + 8 * h),
-                    l1b2 = p32_ld(w.reg, oL1B2 + 8 * h), l2b = p32_ld(w.reg, oL2B + 8 * h),
-                    l2b1 = p32_ld(w.reg, oL2B1 + 8 * h), l2b2 = p32_ld(w.reg, oL2B2 + 8 * h),
-                    lb1 = p32_ld(w.reg, oLB1 + 8 * h), lb2 = p32_ld(w.reg, oLB2 + 8 * h);
+        const uint2 l1b = p32_ld(reg, oL1B + 8 * h), l1b1 = p32_ld(reg, oL1B1 + 8 * h),
+                    l1b2 = p32_ld(reg, oL1B2 + 8 * h), l2b = p32_ld(reg, oL2B + 8 * h),
+                    l2b1 = p32_ld(reg, oL2B1 + 8 * h), l2b2 = p32_ld(reg, oL2B2 + 8 * h),
+                    lb1 = p32_ld(reg, oLB1 + 8 * h), lb2 = p32_ld(reg, oLB2 + 8 * h);
         e[2 * h] = p32_b3<kB3Or3>(p32_b3<kB3AndNor>(l1b.x, l1b1.x, l1b2.x), p32_b3<kB3AndNor>(l2b.x, l2b1.x, l2b2.x),
                                   p32_b3<kB3AndNor>(lb1.x, l1b1.x, l2b1.x)) |
                    p32_b3<kB3AndNor>(lb2.x, l1b2.x, l2b2.x);
@@ -454,8 +531,12 @@ __device__ __forceinline__ void p32_elim(const P32Lane& w, uint32_t tl, uint32_t
 // triad j (column j / 3, box row j % 3); spare lanes read triad 26's column and write their own
 // slots 27..31.
 __device__ __forceinline__ uint32_t p32_locked(const P32Lane& w, P32Cells& x) {
-    const uint32_t j = p32_opq(w.hl), jt = min(j, 26u);
-    const uint32_t tl = jt / 3, tb = jt - 3 * tl;
+    uint32_t j;
+    p32_lds_t* reg;
+    w.place(j, reg);
+    // (jt, tl opaque: see P32Lane::hl)
+    const uint32_t jt = p32_opq(min(j, 26u));
+    const uint32_t tl = p32_opq(jt / 3), tb = jt - 3 * tl;
     const uint32_t ctri = kP32Rec * (27 * tb + tl);
     const uint32_t rtrec = kP32TRec * j, ctrec = kP32ColTri + kP32TRec * j;
     // presence of the lane's row triad (its own cells, closed ones included) and column triad
@@ -464,25 +545,30 @@ __device__ __forceinline__ uint32_t p32_locked(const P32Lane& w, P32Cells& x) {
     for (int d = 0; d < 9; ++d) pr[d] = p32_b3<kB3Or3>(x.c[0][d], x.c[1][d], x.c[2][d]);
 #pragma unroll
     for (int h = 0; h < 5; ++h) {
-        const uint2 b0 = p32_ld(w.reg, ctri + 8 * h), b1 = p32_ld(w.reg, ctri + 360 + 8 * h),
-                    b2 = p32_ld(w.reg, ctri + 720 + 8 * h);
+        const uint2 b0 = p32_ld(reg, ctri + 8 * h), b1 = p32_ld(reg, ctri + 360 + 8 * h),
+                    b2 = p32_ld(reg, ctri + 720 + 8 * h);
         pc[2 * h] = p32_b3<kB3Or3>(b0.x, b1.x, b2.x);
         if (h < 4) pc[2 * h + 1] = p32_b3<kB3Or3>(b0.y, b1.y, b2.y);
     }
     __builtin_amdgcn_wave_barrier();
 #pragma unroll
     for (int h = 0; h < 5; ++h) {
-        p32_st(w.reg, rtrec + 8 * h, pr[2 * h], h < 4 ? pr[2 * h + 1] : 0u);
-        p32_st(w.reg, ctrec + 8 * h, pc[2 * h], h < 4 ? pc[2 * h + 1] : 0u);
+        p32_st(reg, rtrec + 8 * h, pr[2 * h], h < 4 ? pr[2 * h + 1] : 0u);
+        p32_st(reg, ctrec + 8 * h, pc[2 * h], h < 4 ? pc[2 * h + 1] : 0u);
     }
     __builtin_amdgcn_wave_barrier();
-    uint32_t er[9], ec[9];
-    p32_elim(w, tl, tb, 0u, er);
-    p32_elim(w, tl, tb, kP32ColTri, ec);
-    __builtin_amdgcn_wave_barrier();
-    // the column triads' eliminations to LDS (the row triad's are this lane's own cells')
+    // the column triads' eliminations first, and to LDS at once (over the column triads' presence,
+    // which every lane has read by then: one wave, its LDS operations in order), so that their nine
+    // words are not held beside the row triad's -- those are this lane's own cells'
+    uint32_t er[9];
+    {
+        uint32_t ec[9];
+        p32_elim(reg, tl, tb, kP32ColTri, ec);
+        __builtin_amdgcn_wave_barrier();
 #pragma unroll
-    for (int h = 0; h < 5; ++h) p32_st(w.reg, ctrec + 8 * h, ec[2 * h], h < 4 ? ec[2 * h + 1] : 0u);
+        for (int h = 0; h < 5; ++h) p32_st(reg, ctrec + 8 * h, ec[2 * h], h < 4 ? ec[2 * h + 1] : 0u);
+    }
+    p32_elim(reg, tl, tb, 0u, er);
     __builtin_amdgcn_wave_barrier();
     // apply to the lane's open cells: cell 3j + k lies in column 3 (j % 3) + k, box row j / 9, so in
     // column triad 9 (j % 3) + 3k + j / 9
@@ -492,7 +578,7 @@ __device__ __forceinline__ uint32_t p32_locked(const P32Lane& w, P32Cells& x) {
     for (int k = 0; k < 3; ++k) {
 #pragma unroll
         for (int h = 0; h < 5; ++h) {
-            const uint2 c = p32_ld(w.reg, at_c + 3 * kP32TRec * k + 8 * h);
+            const uint2 c = p32_ld(reg, at_c + 3 * kP32TRec * k + 8 * h);
             {
                 const uint32_t rm = (er[2 * h] | c.x) & x.c[k][2 * h] & ~x.s[k];
                 chg |= rm;
@@ -516,7 +602,7 @@ __device__ __forceinline__ uint32_t p32_locked(const P32Lane& w, P32Cells& x) {
 // the batch's last board.  Spare lanes load lane 0's word (masked out like all their results).  A
 // ragged group (nb < 64) loads board nb - 1 in the slots past it (masked out by `valid`).
 __device__ __forceinline__ void p32_load(const uint8_t* src, uint32_t nb, uint32_t (&d)[32]) {
-    const uint32_t t = p32_opq(threadIdx.x), hl = t & 31u, b0 = t & 32u;
+    const uint32_t t = p32_tid(), hl = t & 31u, b0 = t & 32u;
     const uint32_t off = hl < 26u ? 3u * hl : (hl == 26u ? 77u : 0u);
     if (nb == 64u) {
         const uint8_t* p = src + (81u * b0 + off);
@@ -595,7 +681,7 @@ __device__ __forceinline__ uint32_t p32_minterms(const uint32_t (&lo)[4], uint32
 // The lane's 32 loaded words to its three cells' candidate words; returns the boards with a value
 // above 9 in one of the three cells (only the lane's own three bytes of each word enter).
 __device__ __forceinline__ uint32_t p32_convert(const uint32_t (&d)[32], P32Cells& x) {
-    const uint32_t sh = (p32_opq(threadIdx.x) & 31u) == 26u ? 1u : 0u;
+    const uint32_t sh = (p32_tid() & 31u) == 26u ? 1u : 0u;
     uint32_t lo[3][4], hn[4];
 #pragma unroll
     for (int m = 0; m < 4; ++m) {
@@ -666,7 +752,7 @@ struct __attribute__((packed, aligned(4))) p32_u3 {
     uint32_t a, b, c;
 };
 __device__ __forceinline__ void p32_store_group(const p32_lds_t* lds, uint8_t* dst) {
-    const uint32_t t = p32_opq(threadIdx.x);
+    const uint32_t t = p32_tid();
 #pragma unroll
     for (int i = 0; i < 7; ++i) {
         const uint32_t u = t + 64u * i;
@@ -697,7 +783,7 @@ __device__ __forceinline__ uint32_t p32_dequeue(const Prop32Args& a, uint32_t gr
         const uint32_t lo = sg * per, hi = min(lo + per, groups);
         if (lo >= hi) continue;
         uint32_t g = 0;
-        if (threadIdx.x == 0) {
+        if (p32_tid() == 0) {
             // a drained segment: one plain read instead of an atomic that only counts further
             g = __hip_atomic_load(a.heads + sg * kP32HeadStride, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             if (lo + g < hi) g = atomicAdd(a.heads + sg * kP32HeadStride, 1u);
@@ -717,12 +803,12 @@ __device__ __forceinline__ uint32_t p32_dequeue(const Prop32Args& a, uint32_t gr
 __device__ __forceinline__ void p32_answers(const Prop32Args& a, const P32Lane& w, const P32Cells& x, p32_lds_t* lds,
                                             uint64_t base, uint32_t nb, uint64_t solved, uint64_t contra,
                                             uint64_t handed) {
-    if ((solved | handed) && w.act) p32_digits(x, w.reg + 4u * w.hl);
+    if ((solved | handed) && w.act) p32_digits(x, w.reg() + 4u * w.hl());
     for (uint64_t m = contra; m; m &= m - 1ull) {     // rare: the 81 bytes by 64 lanes
-        const uint32_t p = (uint32_t)__builtin_ctzll(m);
+        const uint32_t p = (uint32_t)__builtin_ctzll(m), t = w.tid();
         const uint8_t* s = a.in + (base + p) * 81;
-        lds[p32_stage_byte(p, threadIdx.x)] = s[threadIdx.x];
-        if (threadIdx.x < 17u) lds[p32_stage_byte(p, 64u + threadIdx.x)] = s[64 + threadIdx.x];
+        lds[p32_stage_byte(p, t)] = s[t];
+        if (t < 17u) lds[p32_stage_byte(p, 64u + t)] = s[64 + t];
     }
     __builtin_amdgcn_wave_barrier();
     if (solved | contra) {
@@ -731,7 +817,7 @@ __device__ __forceinline__ void p32_answers(const Prop32Args& a, const P32Lane& 
         if (nb == 64) {
             p32_store_group(lds, dst);
         } else {
-            for (uint32_t o = threadIdx.x; o < nb * 81u; o += 64u) dst[o] = lds[o + o / 3u];
+            for (uint32_t o = w.tid(); o < nb * 81u; o += 64u) dst[o] = lds[o + o / 3u];
         }
     }
 }
@@ -742,21 +828,21 @@ __device__ __forceinline__ void p32_list_undecided(const Prop32Args& a, const p3
                                                    uint32_t me, uint64_t undec, uint64_t handed) {
     if (undec) {
         uint32_t k0 = 0;
-        if (threadIdx.x == 0) k0 = atomicAdd(a.list, (uint32_t)__builtin_popcountll(undec));
+        if (p32_tid() == 0) k0 = atomicAdd(a.list, (uint32_t)__builtin_popcountll(undec));
         k0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)k0);
         if ((undec >> me) & 1ull)
             a.list[1 + k0 + (uint32_t)__builtin_popcountll(undec & ((1ull << me) - 1ull))] = (uint32_t)(base + me);
         uint32_t k = k0;
         for (uint64_t m = undec; m; m &= m - 1ull, ++k) {
-            const uint32_t p = (uint32_t)__builtin_ctzll(m);
+            const uint32_t p = (uint32_t)__builtin_ctzll(m), t = p32_tid();
             uint8_t* d = a.list_in + (uint64_t)k * 81;
             if ((handed >> p) & 1ull) {      // the propagated grid, from the staging
-                d[threadIdx.x] = lds[p32_stage_byte(p, threadIdx.x)];
-                if (threadIdx.x < 17u) d[64 + threadIdx.x] = lds[p32_stage_byte(p, 64u + threadIdx.x)];
+                d[t] = lds[p32_stage_byte(p, t)];
+                if (t < 17u) d[64 + t] = lds[p32_stage_byte(p, 64u + t)];
             } else {
                 const uint8_t* s = a.in + (base + p) * 81;
-                d[threadIdx.x] = s[threadIdx.x];
-                if (threadIdx.x < 17u) d[64 + threadIdx.x] = s[64 + threadIdx.x];
+                d[t] = s[t];
+                if (t < 17u) d[64 + t] = s[64 + t];
             }
         }
     }
@@ -856,7 +942,7 @@ __device__ __forceinline__ uint64_t p32_refute_handed(const P32Lane& w, const p3
 __device__ __forceinline__ void p32_group_end(const Prop32Args& a, const P32Lane& w, const P32Cells& x,
                                               p32_lds_t* lds, const P32Group& G, uint64_t handed) {
     p32_answers(a, w, x, lds, G.base, G.nb, G.solved, G.contra, handed);
-    const uint32_t me = p32_opq(threadIdx.x);        // board me of the group (32 half + hl)
+    const uint32_t me = p32_tid();        // board me of the group (32 half + hl)
     if ((G.valid >> me) & 1ull)
         a.status[G.base + me] =
             (int8_t)(((G.solved >> me) & 1ull) ? 1 : (((G.contra >> me) & 1ull) ? 0 : kStUndecided));
@@ -883,23 +969,21 @@ static __constant__ uint8_t kP32Order[81] = {2, 5, 8, 1, 4, 7, 3, 0, 6, 1, 4, 7,
                                       2, 7, 4, 1, 5, 8, 2, 4, 7, 1, 6, 3, 0, 4, 7, 1, 3, 6, 0, 5, 2, 8, 3, 6, 0,
                                       2, 5, 8, 4, 1, 7};
 
-// p32_unit's per-lane read order, lane L (half L / 32, unit L % 32) at kP32Table + 40 L: 16-bit entry
-// t = the LDS address of the cell of the unit whose kP32Order entry is t, in the lane's half (no
-// per-read address add).  Spare lanes take unit 0's (one more reader of each address).  Written once
-// per workgroup.
+// p32_unit's per-lane read order, unit lane hl (of either half) at kP32Table + kP32TabRec hl: 7-bit
+// field t = the index of the cell of the unit whose kP32Order entry is t (its record: at kP32Rec
+// times that, in the half's region).  Spare lanes take unit 0's (one more reader of each address).
+// Written once per workgroup, by the first half's lanes.
 __device__ __forceinline__ void p32_order_table(p32_lds_t* lds) {
     const uint32_t hl = threadIdx.x & 31u;
     uint32_t u0, ua, ub;
     p32_unit_cells(hl < 27 ? hl : 0u, u0, ua, ub);
-    __attribute__((address_space(3))) uint16_t* tab =
-        (__attribute__((address_space(3))) uint16_t*)(lds + kP32Table + 40u * threadIdx.x);
-    const uint32_t region = (uint32_t)(uintptr_t)lds + (threadIdx.x >> 5) * kP32Region;
+    uint64_t word = 0ull;
     for (uint32_t q = 0; q < 9; ++q) {
-        const uint32_t o = u0 + (q % 3) * ua + (q / 3) * ub;
-        const uint32_t t = kP32Order[o / kP32Rec];
-        static_assert(kP32Lds <= 65536u, "16-bit table entries");
-        tab[t] = (uint16_t)(region + o);
+        const uint32_t cell = (u0 + (q % 3) * ua + (q / 3) * ub) / kP32Rec;
+        word |= (uint64_t)cell << (7u * kP32Order[cell]);
     }
+    if (threadIdx.x < 32u)
+        *(volatile __attribute__((address_space(3))) uint64_t*)(lds + kP32Table + kP32TabRec * hl) = word;
 }
 
 // A wave's set-up, once per workgroup: the order table, and the lane's place in its half.
@@ -907,10 +991,9 @@ __device__ __forceinline__ P32Lane p32_wave_begin(p32_lds_t* lds) {
     p32_order_table(lds);
     __builtin_amdgcn_wave_barrier();
     P32Lane w;
-    w.half = threadIdx.x >> 5;
-    w.hl = threadIdx.x & 31;
-    w.act = w.hl < 27;
-    w.reg = lds + w.half * kP32Region;
+    w.act = (threadIdx.x & 31u) < 27u;
+    w.lds = lds;
+    w.pk = (threadIdx.x & 31u) | ((threadIdx.x >> 5) * kP32Region) << 16;
     return w;
 }
 

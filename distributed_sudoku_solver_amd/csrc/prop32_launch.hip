@@ -35,7 +35,7 @@ __global__ void p32_scatter_kernel(const uint32_t* list, const uint8_t* sub_out,
 }
 
 #ifndef SDK_PROP32_WAVES_PER_EU
-#define SDK_PROP32_WAVES_PER_EU 4
+#define SDK_PROP32_WAVES_PER_EU 5
 #endif
 // The kernel body; kStamp (prop32_clock_kernel, a diagnostic twin: the timed kernel runs no stamp)
 // writes s_memtime (shader clock) and s_memrealtime (100 MHz) at a workgroup's entry and exit to
@@ -43,12 +43,16 @@ __global__ void p32_scatter_kernel(const uint32_t* list, const uint8_t* sub_out,
 // their ratio (MI355X_MICROARCH.md, "DVFS give-back" item 6), the clock the VALU roofline prices
 template <bool kStamp>
 __device__ __forceinline__ void prop32_body(Prop32Args a, uint64_t* stamps) {
-    __shared__ __attribute__((aligned(16))) uint8_t s_lds[kP32Lds];
+    // (kStamp: eight bytes more, where the workgroup's stamp address waits for the exit -- held in
+    // scalar registers through the loop it is the pair that no longer fits, and a scalar register
+    // spilled costs the kernel a vector register, which costs it the fifth wave)
+    __shared__ __attribute__((aligned(16))) uint8_t s_lds[kP32Lds + (kStamp ? 8u : 0u)];
     p32_lds_t* const lds = (p32_lds_t*)s_lds;
     if (kStamp && threadIdx.x == 0) {    // (stored at once: no register holds them through the loop)
         uint64_t* o = stamps + 4u * blockIdx.x;
         o[0] = __builtin_amdgcn_s_memtime();
         o[1] = __builtin_amdgcn_s_memrealtime();
+        *(volatile __attribute__((address_space(3))) uint64_t*)(lds + kP32Lds) = (uint64_t)(uintptr_t)o;
     }
     const P32Lane w = p32_wave_begin(lds);
     const uint32_t groups = (uint32_t)((a.n + 63) / 64);
@@ -133,8 +137,8 @@ __device__ __forceinline__ void prop32_body(Prop32Args a, uint64_t* stamps) {
     }
     if (kStamp) {
         const uint64_t t1 = __builtin_amdgcn_s_memtime(), r1 = __builtin_amdgcn_s_memrealtime();
-        if (threadIdx.x == 0) {
-            uint64_t* o = stamps + 4u * blockIdx.x;
+        if (p32_tid() == 0) {
+            uint64_t* o = (uint64_t*)(uintptr_t)(*(volatile __attribute__((address_space(3))) uint64_t*)(lds + kP32Lds));
             o[2] = t1;
             o[3] = r1;
         }
