@@ -30,6 +30,9 @@ SDK_GRADE_NAKED = 1
 SDK_GRADE_HIDDEN = 2
 SDK_GRADE_LOCKED = 3
 SDK_GRADE_SEARCH = 4
+# sdk_generate_graded: every level (bits 1..4 of level_mask), the largest explicit chunk
+SDK_GRADE_MASK_ALL = 0x1E
+SDK_GRADED_CHUNK_MAX = 1 << 24
 
 SDK_CHECK_OK = 1
 SDK_CHECK_RAW_NAMEERROR = 2
@@ -125,6 +128,14 @@ SIGNATURES = {
     "sdk_generate_grids_dev": (ctypes.c_int, [_vp, ctypes.c_uint64, ctypes.c_uint64, _sz, _vp, _vp, _vp]),
     "sdk_generate_puzzles": (ctypes.c_int, [_vp, ctypes.c_uint64, ctypes.c_uint64, _sz, _vp, _vp, _vp]),
     "sdk_generate_puzzles_dev": (ctypes.c_int, [_vp, ctypes.c_uint64, ctypes.c_uint64, _sz, _vp, _vp, _vp]),
+    "sdk_generate_graded": (ctypes.c_int, [_vp, ctypes.c_uint64, ctypes.c_uint64, _sz, ctypes.c_uint32,
+                                           ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint64,
+                                           _vp, _vp, _vp, _vp, _vp, ctypes.POINTER(ctypes.c_uint64),
+                                           ctypes.POINTER(ctypes.c_uint64)]),
+    "sdk_generate_graded_dev": (ctypes.c_int, [_vp, ctypes.c_uint64, ctypes.c_uint64, _sz, ctypes.c_uint32,
+                                               ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint64,
+                                               _vp, _vp, _vp, _vp, _vp, ctypes.POINTER(ctypes.c_uint64),
+                                               ctypes.POINTER(ctypes.c_uint64)]),
     "sdk_frontier_boards_dev": (ctypes.c_int, [_vp, ctypes.POINTER(_vp), ctypes.POINTER(ctypes.c_uint64)]),
     "sdk_frontier_load_dev": (ctypes.c_int, [_vp, _vp, ctypes.c_uint64]),
     "sdk_frontier_refine_range": (ctypes.c_int, [_vp, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64,

@@ -375,6 +375,11 @@ struct sdk_ctx {
     int64_t gen_cap = 1 << 20;     // SDK_OPT_GEN_CAP: a generated grid is kept iff its fill placed at most this many digits
     DevBuf gen_order;              // sdk_generate_puzzles: a slice's removal orders
     DevBuf gen_plc;                // sdk_generate_grids (host pointers): the placement counts
+    // sdk_generate_graded: a round's candidates (puzzles, grids, generator status), their grading
+    // (completions and verdicts nobody reads, level, open count) and selection (per tile of 64 rows:
+    // ballot, popcount, offset); the call's device word (sdk::SelWord); the host-pointer call's outputs
+    DevBuf gg_puz, gg_grid, gg_st, gg_sol, gg_gst, gg_level, gg_open, gg_ballot, gg_count, gg_offset, gg_word;
+    DevBuf gg_out_puz, gg_out_grid, gg_out_level, gg_out_open, gg_out_index;
     DevBuf fr_a, fr_b, prop, bcell, bmask, nchild, offs, fr_status, fr_mask, tsum, fr_ctl;
     DevBuf fr_tail;                // refine_head: the boards kept after the refined ones
     // the device-resident frontier of the last sdk_frontier_build (in fr_a)
@@ -491,14 +496,14 @@ struct Piece {
 };
 
 // The copies of a host-pointer call: send() before the launch, fetch() after it (it synchronizes).
-// The (at most four) pieces lie in the pinned area (HostBuf) in the order given -- widest element
+// The (at most five) pieces lie in the pinned area (HostBuf) in the order given -- widest element
 // type first, so every slot is aligned for its type; a call too large for the area copies straight
 // from / to the caller's pageable memory.  An error return between send() and the end of fetch()
 // may leave copies from / into the area queued, so the stream is drained first: the next call's
 // memcpy into the area (or a grow that frees it) cannot race them.
 class Staging {
     sdk_ctx* c;
-    Piece p[4];
+    Piece p[5];
     int np = 0;
     bool armed = true;
 
@@ -1202,6 +1207,142 @@ int check_generate_args(uint64_t first, size_t n) {
     int rc;
     if ((rc = check_board_count(n))) return rc;
     if (first > UINT64_MAX - (uint64_t)n) return fail(SDK_EINVAL, "first + n overflows the stream index");
+    return SDK_OK;
+}
+
+// Graded generation (sdk_generate_graded; select_kernel.h): the window [first, first + max_scan) in
+// rounds of m stream indices.  A round is launch_generate_puzzles into the context's work buffers,
+// launch_grade of those puzzles with no budget (completions and verdicts to scratch: grading in place
+// would overwrite the puzzles), the three selection launches behind the hits of the earlier rounds,
+// and ONE 8-byte readback of the call's device word -- the only host round trip.  The scan stops when
+// the word's total reaches n or the window ends.  The outputs depend on the rounds in no way: a
+// round's hits are ranked behind all earlier ones, ranks >= n are never written, and `scanned` comes
+// from the position of the hit of rank n - 1 (SelWord::last), not from the rounds run.
+//   chunk != 0: every round is min(chunk, rest of the window) indices.
+//   chunk == 0: the first round is 4 n indices, a later one what the hit rate so far asks for the
+//               missing hits plus a quarter (twice the last round while nothing was hit), each within
+//               kGradedAutoMin .. kGradedAutoMax.
+// The work buffers hold whole tiles of 64 rows (the selection kernels load whole tiles).  One span
+// under SDK_OPT_TIMING.  The outputs are device pointers; *found / *scanned are the host's.
+constexpr uint64_t kGradedChunkMax = 1ull << 24;   // = kDnCapBoards: a round is one slice of generate and grade
+constexpr uint64_t kGradedAutoMin = 4096, kGradedAutoMax = 1ull << 20;
+
+struct GradedCall {
+    uint64_t seed, first;
+    uint32_t n;
+    uint32_t level_mask, clues_lo, clues_hi;
+    uint64_t max_scan, chunk;
+    uint8_t *puzzles, *grids, *level, *open;
+    uint64_t* index;
+};
+
+int launch_generate_graded(sdk_ctx* c, const GradedCall& g, uint64_t* found, uint64_t* scanned) {
+    if ((reinterpret_cast<uintptr_t>(g.puzzles) | reinterpret_cast<uintptr_t>(g.grids)) & 15u)
+        return fail(SDK_EINVAL, "device boards must be 16-byte aligned");
+    if (reinterpret_cast<uintptr_t>(g.index) & 7u) return fail(SDK_EINVAL, "index must be 8-byte aligned");
+    int rc;
+    if ((rc = ensure(c->gg_word, sizeof(sdk::SelWord)))) return rc;
+    sdk::SelWord* d_word = static_cast<sdk::SelWord*>(c->gg_word.p);
+    TimedSpan span(c);
+    if ((rc = span.begin())) return rc;
+    HIPCALL(hipMemsetAsync(d_word, 0, sizeof(sdk::SelWord), c->stream));
+    uint64_t done = 0, hits = 0, last_m = 0;
+    while (done < g.max_scan) {
+        const uint64_t rest = g.max_scan - done;
+        uint64_t m = g.chunk;
+        if (!m) {
+            if (!done)
+                m = 4ull * g.n;
+            else if (!hits)
+                m = 2 * last_m;
+            else {
+                // (n - hits) < 2^31 and done < 2^64 / 2^31 whenever the product matters: the quotient is
+                // clamped to 2^20 anyway, so saturate instead of overflowing
+                const uint64_t miss = g.n - hits;
+                const uint64_t need = done > UINT64_MAX / miss ? kGradedAutoMax : miss * done / hits;
+                m = need + need / 4;
+            }
+            m = std::min(std::max(m, kGradedAutoMin), kGradedAutoMax);
+        }
+        m = std::min(m, rest);
+        last_m = m;
+        const uint32_t tiles = (uint32_t)((m + sdk::kSelTileRows - 1) / sdk::kSelTileRows);
+        const size_t rows = (size_t)tiles * sdk::kSelTileRows;
+        if ((rc = ensure(c->gg_puz, rows * 81)) || (rc = ensure(c->gg_grid, rows * 81)) ||
+            (rc = ensure(c->gg_sol, rows * 81)) || (rc = ensure(c->gg_st, rows)) || (rc = ensure(c->gg_gst, rows)) ||
+            (rc = ensure(c->gg_level, rows)) || (rc = ensure(c->gg_open, rows)) ||
+            (rc = ensure(c->gg_ballot, (size_t)tiles * 8)) || (rc = ensure(c->gg_count, (size_t)tiles * 4)) ||
+            (rc = ensure(c->gg_offset, (size_t)tiles * 4)))
+            return rc;
+        uint8_t* puz = static_cast<uint8_t*>(c->gg_puz.p);
+        uint8_t* grid = static_cast<uint8_t*>(c->gg_grid.p);
+        int8_t* st = static_cast<int8_t*>(c->gg_st.p);
+        uint8_t* level = static_cast<uint8_t*>(c->gg_level.p);
+        uint8_t* open = static_cast<uint8_t*>(c->gg_open.p);
+        if ((rc = launch_generate_puzzles(c, g.seed, g.first + done, m, puz, grid, st)) ||
+            (rc = launch_grade(c, puz, static_cast<uint8_t*>(c->gg_sol.p), static_cast<int8_t*>(c->gg_gst.p), level,
+                               open, m, 0)))
+            return rc;
+        sdk::SelFlagArgs fa{};
+        fa.puzzles = puz;
+        fa.status = st;
+        fa.level = level;
+        fa.m = (uint32_t)m;
+        fa.level_mask = g.level_mask;
+        fa.clues_lo = g.clues_lo;
+        fa.clues_hi = g.clues_hi;
+        fa.ballot = static_cast<unsigned long long*>(c->gg_ballot.p);
+        fa.count = static_cast<uint32_t*>(c->gg_count.p);
+        sdk::SelScanArgs sa{};
+        sa.count = fa.count;
+        sa.offset = static_cast<uint32_t*>(c->gg_offset.p);
+        sa.tiles = tiles;
+        sa.word = d_word;
+        sdk::SelScatterArgs ca{};
+        ca.puzzles = puz;
+        ca.grids = grid;
+        ca.level = level;
+        ca.open = open;
+        ca.ballot = fa.ballot;
+        ca.offset = sa.offset;
+        ca.first = g.first + done;
+        ca.n = g.n;
+        ca.out_puzzles = g.puzzles;
+        ca.out_grids = g.grids;
+        ca.out_level = g.level;
+        ca.out_open = g.open;
+        ca.out_index = g.index;
+        ca.word = d_word;
+        HIPCALL(sdk::launch_select_flag(fa, tiles, c->stream));
+        HIPCALL(sdk::launch_select_scan(sa, c->stream));
+        HIPCALL(sdk::launch_select_scatter(ca, tiles, c->stream));
+        sdk::SelWord word;
+        HIPCALL(hipMemcpyAsync(&word, d_word, sizeof word, hipMemcpyDeviceToHost, c->stream));
+        HIPCALL(hipStreamSynchronize(c->stream));
+        hits = word.total;
+        if (hits >= g.n) {
+            if (word.last == 0 || word.last > m) return fail(SDK_EHIP, "graded selection lost the position of its last hit");
+            *found = g.n;
+            *scanned = done + word.last;
+            return span.end(SDK_OK);
+        }
+        done += m;
+    }
+    *found = hits;
+    *scanned = g.max_scan;
+    return span.end(SDK_OK);
+}
+
+// argument checks of sdk_generate_graded and its _dev form
+int check_graded_args(uint64_t first, size_t n, uint32_t level_mask, uint32_t clues_lo, uint32_t clues_hi,
+                      uint64_t max_scan, uint64_t chunk) {
+    int rc;
+    if ((rc = check_board_count(n))) return rc;
+    if (level_mask == 0 || (level_mask & ~0x1Eu)) return fail(SDK_EINVAL, "level_mask must be a non-empty set of bits 1..4");
+    if (clues_lo > clues_hi || clues_hi > 81) return fail(SDK_EINVAL, "clue range must be clues_lo <= clues_hi <= 81");
+    if (max_scan == 0) return fail(SDK_EINVAL, "max_scan must be at least 1");
+    if (first > UINT64_MAX - max_scan) return fail(SDK_EINVAL, "first + max_scan overflows the stream index");
+    if (chunk > kGradedChunkMax) return fail(SDK_EINVAL, "chunk must be 0 (automatic) or 1..2^24");
     return SDK_OK;
 }
 
@@ -2158,6 +2299,68 @@ int sdk_generate_puzzles(sdk_ctx* c, uint64_t seed, uint64_t first, size_t n, ui
                    {n, nullptr, nullptr, d_status, status}});
     if ((rc = launch_generate_puzzles(c, seed, first, n, d_puzzles, d_grids, d_status))) return rc;
     return io.fetch();
+}
+
+int sdk_generate_graded_dev(sdk_ctx* c, uint64_t seed, uint64_t first, size_t n, uint32_t level_mask,
+                            uint32_t clues_lo, uint32_t clues_hi, uint64_t max_scan, uint64_t chunk, void* d_puzzles,
+                            void* d_grids, void* d_level, void* d_open, void* d_index, uint64_t* found,
+                            uint64_t* scanned) {
+    if (!c || !found || (n && (!d_puzzles || !d_grids))) return fail(SDK_EINVAL, "NULL argument");
+    int rc;
+    if ((rc = check_graded_args(first, n, level_mask, clues_lo, clues_hi, max_scan, chunk))) return rc;
+    if ((reinterpret_cast<uintptr_t>(d_puzzles) | reinterpret_cast<uintptr_t>(d_grids)) & 15u)
+        return fail(SDK_EINVAL, "device boards must be 16-byte aligned");
+    if (reinterpret_cast<uintptr_t>(d_index) & 7u) return fail(SDK_EINVAL, "d_index must be 8-byte aligned");
+    uint64_t f = 0, s = 0;
+    if (n) {
+        std::lock_guard<std::mutex> lk(c->mu);
+        HIPCALL(hipSetDevice(c->device));
+        const GradedCall g{seed, first, (uint32_t)n, level_mask, clues_lo, clues_hi, max_scan, chunk,
+                           static_cast<uint8_t*>(d_puzzles), static_cast<uint8_t*>(d_grids),
+                           static_cast<uint8_t*>(d_level), static_cast<uint8_t*>(d_open),
+                           static_cast<uint64_t*>(d_index)};
+        if ((rc = launch_generate_graded(c, g, &f, &s))) return rc;
+    }
+    *found = f;
+    if (scanned) *scanned = s;
+    return SDK_OK;
+}
+
+int sdk_generate_graded(sdk_ctx* c, uint64_t seed, uint64_t first, size_t n, uint32_t level_mask, uint32_t clues_lo,
+                        uint32_t clues_hi, uint64_t max_scan, uint64_t chunk, uint8_t* puzzles, uint8_t* grids,
+                        uint8_t* level, uint8_t* open, uint64_t* index, uint64_t* found, uint64_t* scanned) {
+    if (!c || !found || (n && (!puzzles || !grids))) return fail(SDK_EINVAL, "NULL argument");
+    int rc;
+    if ((rc = check_graded_args(first, n, level_mask, clues_lo, clues_hi, max_scan, chunk))) return rc;
+    uint64_t f = 0, s = 0;
+    if (n) {
+        std::lock_guard<std::mutex> lk(c->mu);
+        HIPCALL(hipSetDevice(c->device));
+        // at most min(n, max_scan) rows can come back
+        const size_t rows = (size_t)std::min<uint64_t>(n, max_scan);
+        if ((rc = ensure(c->gg_out_puz, rows * 81)) || (rc = ensure(c->gg_out_grid, rows * 81)) ||
+            (level && (rc = ensure(c->gg_out_level, rows))) || (open && (rc = ensure(c->gg_out_open, rows))) ||
+            (index && (rc = ensure(c->gg_out_index, rows * 8))))
+            return rc;
+        const GradedCall g{seed, first, (uint32_t)n, level_mask, clues_lo, clues_hi, max_scan, chunk,
+                           static_cast<uint8_t*>(c->gg_out_puz.p), static_cast<uint8_t*>(c->gg_out_grid.p),
+                           level ? static_cast<uint8_t*>(c->gg_out_level.p) : nullptr,
+                           open ? static_cast<uint8_t*>(c->gg_out_open.p) : nullptr,
+                           index ? static_cast<uint64_t*>(c->gg_out_index.p) : nullptr};
+        if ((rc = launch_generate_graded(c, g, &f, &s))) return rc;
+        if (f) {
+            // the rows found, and nothing behind them
+            Staging io(c, {{index ? f * 8 : 0, nullptr, nullptr, g.index, index},
+                           {f * 81, nullptr, nullptr, g.puzzles, puzzles},
+                           {f * 81, nullptr, nullptr, g.grids, grids},
+                           {level ? f : 0, nullptr, nullptr, g.level, level},
+                           {open ? f : 0, nullptr, nullptr, g.open, open}});
+            if ((rc = io.fetch())) return rc;
+        }
+    }
+    *found = f;
+    if (scanned) *scanned = s;
+    return SDK_OK;
 }
 
 int sdk_count_solutions(sdk_ctx* c, const uint8_t* board, uint64_t limit, uint64_t* count, int8_t* status) {

@@ -388,6 +388,52 @@ class SudokuEngine:
                 "sdk_generate_puzzles")
         return puzzles, grids, status
 
+    @staticmethod
+    def _graded_args(n, levels, seed, lo, clues, max_scan, chunk):
+        """The arguments of sdk_generate_graded from generate_graded's (ValueError for a bad one)."""
+        n, seed, lo = SudokuEngine._stream_rows(n, seed, lo)
+        if n >= 1 << 31:
+            raise ValueError("n must be below 2^31")
+        levels = [int(v) for v in levels]
+        if not levels or any(not 1 <= v <= 4 for v in levels):
+            raise ValueError("levels must be a non-empty selection of 1, 2, 3, 4")
+        mask = 0
+        for v in levels:
+            mask |= 1 << v
+        clues_lo, clues_hi = (0, 81) if clues is None else (int(clues[0]), int(clues[1]))
+        if not 0 <= clues_lo <= clues_hi <= 81:
+            raise ValueError("clues must be (lo, hi) with 0 <= lo <= hi <= 81")
+        max_scan, chunk = int(max_scan), int(chunk)
+        if max_scan < 1 or lo + max_scan >= 1 << 64:
+            raise ValueError("max_scan must be >= 1 and lo + max_scan an unsigned 64-bit integer")
+        if not 0 <= chunk <= L.SDK_GRADED_CHUNK_MAX:
+            raise ValueError("chunk must be 0 (automatic) or 1..2^24")
+        return seed, lo, n, mask, clues_lo, clues_hi, max_scan, chunk
+
+    def generate_graded(self, n, levels=(1, 2, 3, 4), seed=synth.DEFAULT_SEED + 3, lo=0, clues=None,
+                        max_scan=1 << 26, chunk=0):
+        """The first n puzzles of generate_batch's stream, from row lo on, whose grade_batch level is one
+        of `levels` and whose clue count lies in clues = (lo, hi) (None: any), made, graded and selected
+        on the GPU (sdk_generate_graded): (puzzles uint8[found,81], solutions uint8[found,81], level
+        uint8[found], open uint8[found], index uint64[found], scanned).  At most max_scan rows are
+        looked at, so found <= n; index holds the stream rows of the puzzles, ascending; scanned is the
+        number of rows up to and including the n-th match (max_scan if there were fewer).  chunk is the
+        number of rows per round (0 = automatic): it changes speed and memory only, never the result.
+        A bad argument raises ValueError before any launch."""
+        args = self._graded_args(n, levels, seed, lo, clues, max_scan, chunk)
+        rows = min(args[2], args[6])
+        puzzles = np.empty((rows, 81), dtype=np.uint8)
+        grids = np.empty((rows, 81), dtype=np.uint8)
+        level = np.empty(rows, dtype=np.uint8)
+        open_ = np.empty(rows, dtype=np.uint8)
+        index = np.empty(rows, dtype=np.uint64)
+        found, scanned = ctypes.c_uint64(), ctypes.c_uint64()
+        L.check(self.lib.sdk_generate_graded(self.ctx, *args, _ptr(puzzles), _ptr(grids), _ptr(level), _ptr(open_),
+                                             _ptr(index), ctypes.byref(found), ctypes.byref(scanned)),
+                "sdk_generate_graded")
+        f = found.value
+        return puzzles[:f], grids[:f], level[:f], open_[:f], index[:f], scanned.value
+
     def expand(self, boards, masks=None, target=64):
         """Lex-ordered frontier below `boards` (sdk_expand_boards): uint8[k,81], children in the
         reference's DFS order, parents' order kept; at least one level, >= target boards unless
@@ -585,3 +631,17 @@ class SudokuEngine:
         L.check(self.lib.sdk_generate_puzzles_dev(self.ctx, int(seed), int(lo), int(n), d_puzzles.ptr, d_grids.ptr,
                                                   d_status.ptr),
                 "sdk_generate_puzzles_dev")
+
+    def generate_graded_dev(self, d_puzzles, d_grids, n, levels=(1, 2, 3, 4), seed=synth.DEFAULT_SEED + 3, lo=0,
+                            clues=None, max_scan=1 << 26, chunk=0, d_level=None, d_open=None, d_index=None):
+        """generate_graded into device buffers of n rows (d_puzzles, d_grids 16-byte aligned; the others
+        optional): -> (found, scanned).  Rows from `found` on are left as they were; the rows are valid
+        after synchronize()."""
+        args = self._graded_args(n, levels, seed, lo, clues, max_scan, chunk)
+        found, scanned = ctypes.c_uint64(), ctypes.c_uint64()
+        L.check(self.lib.sdk_generate_graded_dev(self.ctx, *args, d_puzzles.ptr, d_grids.ptr,
+                                                 d_level.ptr if d_level else None, d_open.ptr if d_open else None,
+                                                 d_index.ptr if d_index else None, ctypes.byref(found),
+                                                 ctypes.byref(scanned)),
+                "sdk_generate_graded_dev")
+        return found.value, scanned.value

@@ -45,7 +45,7 @@ extern "C" {
 #define SDK_ABI_VERSION 2   /* 2: sdk_solve_batch_ex, frontier records, p2p send/recv; version 2 */
                             /* also gained sdk_classify_batch[_dev] and sdk_minimize_batch[_dev]  */
                             /* and sdk_generate_grids[_dev] / sdk_generate_puzzles[_dev]          */
-                            /* and sdk_grade_batch[_dev]                                          */
+                            /* and sdk_grade_batch[_dev] and sdk_generate_graded[_dev]            */
                             /* (new symbols only: nothing a version-2 caller uses changed)        */
 
 /* return codes */
@@ -316,6 +316,44 @@ int sdk_generate_grids(sdk_ctx *ctx, uint64_t seed, uint64_t first, size_t n, ui
 int sdk_generate_puzzles(sdk_ctx *ctx, uint64_t seed, uint64_t first, size_t n, uint8_t *puzzles,
                          uint8_t *grids, int8_t *status);
 
+/* Puzzles of a requested grade: the first n puzzles of the stream, from index `first` on, that match
+ * a predicate -- generated, graded and selected on the GPU; only the matches leave the device.
+ *
+ * Candidate k is row k of sdk_generate_puzzles(seed, ...).  Its level and open count are the ones
+ * sdk_grade_batch gives that puzzle with no node budget (the context's SDK_OPT_NODE_BUDGET has no
+ * effect, as in the minimiser); its clue count is the number of its non-zero cells.  Candidate k is a
+ * hit when its generator status is SDK_SOLVED, bit `level` of level_mask is set and
+ * clues_lo <= clues <= clues_hi.  A grid dropped by SDK_OPT_GEN_CAP is a row of zeros of level
+ * SDK_GRADE_NONE: never a hit.
+ *
+ * The window is [first, first + max_scan).  *found = min(n, hits in the window).  For j < *found, with
+ * k_j the j-th smallest hit: puzzles[j] and grids[j] are its puzzle and its completion, level[j] and
+ * open[j] its grade, index[j] = k_j.  Rows j >= *found are not written, in either form (the host form
+ * copies *found rows back).  *scanned = k_(n-1) - first + 1 when *found == n, else max_scan: a number
+ * of the result, not of the work done.  The result is a pure function of (seed, first, n, level_mask,
+ * clues_lo, clues_hi, max_scan, SDK_OPT_GEN_CAP).
+ *
+ *   level_mask  a non-empty set of bits SDK_GRADE_NAKED..SDK_GRADE_SEARCH (1..4), else SDK_EINVAL;
+ *   clues_lo <= clues_hi <= 81;  max_scan >= 1, and first + max_scan must not overflow;
+ *   n           as in the other generate calls (at most 2^31-1); n == 0 launches nothing and gives
+ *               *found = *scanned = 0;
+ *   chunk       stream indices per round, 0 = automatic, or 1..2^24.  The window is scanned in rounds
+ *               (generate, grade, then three selection launches: select_kernel.h) until n hits are
+ *               found or it ends; the last round may look past `scanned`.  chunk changes speed and
+ *               work memory (about 250 bytes per index of a round), never a byte of the result.
+ *               Automatic: the first round is 4 n indices; a later one is what the hit rate so far
+ *               asks for the missing hits, plus a quarter (twice the round before while there was no
+ *               hit yet); every automatic round is within 4096..2^20 indices and the window.
+ *   puzzles, grids  uint8[n][81], required;  level, open  uint8[n], index  uint64[n], scanned: nullable;
+ *   found       required.
+ * The call holds the context for all its rounds and reads one 8-byte count back per round, its only
+ * host round trip.  It changes no option; under SDK_OPT_TIMING it records one span. */
+int sdk_generate_graded(sdk_ctx *ctx, uint64_t seed, uint64_t first, size_t n,
+                        uint32_t level_mask, uint32_t clues_lo, uint32_t clues_hi,
+                        uint64_t max_scan, uint64_t chunk,
+                        uint8_t *puzzles, uint8_t *grids, uint8_t *level, uint8_t *open,
+                        uint64_t *index, uint64_t *found, uint64_t *scanned);
+
 /* The worklist step of a resumable lex-first search of a board whose solve hit the
  * budget (distributed_sudoku_solver_amd/search.py; the in-node form of handing a
  * subtree on, DHT_Node.py:491-510): expand n boards -- board i with first-cell mask
@@ -477,6 +515,15 @@ int sdk_generate_grids_dev(sdk_ctx *ctx, uint64_t seed, uint64_t first, size_t n
                            void *d_order, void *d_placements);
 int sdk_generate_puzzles_dev(sdk_ctx *ctx, uint64_t seed, uint64_t first, size_t n, void *d_puzzles,
                              void *d_grids, void *d_status);
+/* d_puzzles and d_grids 16-byte aligned (and d_index 8-byte), else SDK_EINVAL; d_level, d_open,
+ * d_index and scanned nullable; found and scanned are host pointers.  The call returns when the scan
+ * is decided (it waits for every round's count): *found and *scanned are final then, and the device
+ * rows are valid after sdk_synchronize.  Rows from *found on are not written. */
+int sdk_generate_graded_dev(sdk_ctx *ctx, uint64_t seed, uint64_t first, size_t n,
+                            uint32_t level_mask, uint32_t clues_lo, uint32_t clues_hi,
+                            uint64_t max_scan, uint64_t chunk,
+                            void *d_puzzles, void *d_grids, void *d_level, void *d_open,
+                            void *d_index, uint64_t *found, uint64_t *scanned);
 
 /* Kernel time accounting (HIP events on the context stream, bracketing every
  * kernel launched by the *_dev / host calls since the last reset).  Only with
