@@ -48,8 +48,6 @@
 
 namespace sdk {
 
-constexpr uint32_t kG32MaxSteps = 768;   // > 729 + 3 (see above)
-
 // SDK_GRADE32_STATS (profiling builds only): per group, histograms of the unit/cells steps it ran and
 // of its locked passes (tools/bench_grade.py --stats reads them)
 #ifndef SDK_GRADE32_STATS

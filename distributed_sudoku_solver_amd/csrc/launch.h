@@ -8,6 +8,7 @@
 #include "donate_args.h"
 #include "frontier_args.h"
 #include "prop32_args.h"
+#include "rate_args.h"
 #include "select_args.h"
 #include "solve_args.h"
 
@@ -27,6 +28,9 @@ hipError_t launch_p32_scatter(const uint32_t* list, const uint8_t* sub_out, cons
 hipError_t launch_grade32(const Grade32Args& a, unsigned grid, hipStream_t stream);
 hipError_t launch_g32_verdict(const uint32_t* list, const int8_t* sub_st, uint8_t* level, uint8_t* open,
                               unsigned grid, hipStream_t stream);
+
+// rate32_launch.hip: one wave per level-4 board of the grade pass's list (its length is on the device)
+hipError_t launch_rate32(const Rate32Args& a, unsigned grid, hipStream_t stream);
 
 // select_launch.hip: one wave per tile of 64 rows (flag, scatter), one workgroup (scan)
 hipError_t launch_select_flag(const SelFlagArgs& a, uint32_t tiles, hipStream_t stream);

@@ -8,6 +8,10 @@ namespace sdk {
 constexpr uint32_t kP32Heads = 8;        // dequeue counters, one per XCD segment of the groups
 constexpr uint32_t kP32HeadStride = 32;  // words between counters (own cache lines)
 
+// the step limit of the passes that run to a fixpoint (the grading pass, grade32_kernel.h, where the
+// bound is derived; the rating pass, rate32_kernel.h): a termination guard, never a hand-off
+constexpr uint32_t kG32MaxSteps = 768;   // > 729 + 3
+
 struct Prop32Args {
     const uint8_t* in;       // boards [n][81]; 16-byte aligned
     uint8_t* out;            // [n][81]; 16-byte aligned

@@ -1,5 +1,5 @@
 // select_args.h -- arguments of the selection kernels (select_kernel.h, select_launch.hip): the
-// order-preserving compaction of a round of sdk_generate_graded, shared with its driver in
+// order-preserving compaction of a round of sdk_generate_graded / sdk_generate_rated, shared with its driver in
 // sudoku_hip.hip (launch_generate_graded).
 #pragma once
 #include <cstdint>
@@ -28,6 +28,8 @@ struct SelFlagArgs {
     const uint8_t* level;        // [m] grade
     uint32_t m;
     uint32_t level_mask, clues_lo, clues_hi;
+    const uint8_t* backdoors;    // [m] rating, nullable (sdk_generate_rated): a level-4 row is a hit only
+    uint32_t bd_lo, bd_hi;       // with bd_lo <= backdoors <= bd_hi; rows of other levels are not filtered
     unsigned long long* ballot;  // [tiles] bit l = row 64 t + l is a hit
     uint32_t* count;             // [tiles] its popcount
 };
@@ -53,6 +55,10 @@ struct SelScatterArgs {
     uint8_t* out_level;          // [n], nullable
     uint8_t* out_open;           // [n], nullable
     uint64_t* out_index;         // [n], nullable
+    const uint8_t* backdoors;    // the round's ratings, nullable: SDK_RATE_NONE goes out instead
+    const uint8_t* key;
+    uint8_t* out_backdoors;      // [n], nullable
+    uint8_t* out_key;            // [n], nullable
     SelWord* word;
 };
 

@@ -6,7 +6,8 @@
 // rounds:
 //   flag     one wave per tile of 64 consecutive rows.  The tile (5,184 bytes, 16-byte aligned) goes
 //            to LDS in 16-byte pieces; each lane then counts the clues of its own row, evaluates the
-//            predicate (status SDK_SOLVED, bit `level` of the mask, clues_lo <= clues <= clues_hi) and
+//            predicate (status SDK_SOLVED, bit `level` of the mask, clues_lo <= clues <= clues_hi; with
+//            ratings, sdk_generate_rated: a level-4 row also bd_lo <= backdoors <= bd_hi) and
 //            the wave stores its 64-bit ballot and the ballot's popcount.
 //   scan     ONE workgroup loops over the tile counts (a round of 2^24 rows has 262,144 of them): an
 //            exclusive prefix sum that starts at the hits found so far (SelWord::total) and leaves
@@ -20,7 +21,7 @@
 //            output's own 16-byte phase, the 16-byte pieces that lie wholly inside the range are
 //            stored as such, and the (at most 15 + 15) bytes before and after them one byte each:
 //            no store touches a byte outside the tile's range and nothing is read-modify-written.
-//            Level, open count and stream index go out per hit; the hit of rank n - 1 also leaves
+//            Level, open count, stream index and the ratings go out per hit; the hit of rank n - 1 also leaves
 //            its round row (+ 1) in SelWord::last, from which the host computes `scanned`.
 //
 // Bounds: the work buffers hold whole tiles, so the 16-byte tile loads stay inside them for a last
@@ -54,6 +55,10 @@ __global__ __launch_bounds__(64) void select_flag_kernel(SelFlagArgs a) {
     if (row < a.m && a.status[row] == 1) {
         const uint32_t lv = a.level[row];
         hit = lv < 32u && ((a.level_mask >> lv) & 1u) && clues >= a.clues_lo && clues <= a.clues_hi;
+        if (hit && a.backdoors && lv == 4u) {       // rated generation: the search-level rows by their rating
+            const uint32_t bd = a.backdoors[row];
+            hit = bd >= a.bd_lo && bd <= a.bd_hi;
+        }
     }
     const unsigned long long b = __ballot(hit);
     if (lane == 0) {
@@ -107,6 +112,8 @@ __global__ __launch_bounds__(64) void select_scatter_kernel(SelScatterArgs a) {
         if (a.out_level) a.out_level[rank] = a.level[row];
         if (a.out_open) a.out_open[rank] = a.open[row];
         if (a.out_index) a.out_index[rank] = a.first + row;
+        if (a.out_backdoors) a.out_backdoors[rank] = a.backdoors ? a.backdoors[row] : (uint8_t)0xFFu;
+        if (a.out_key) a.out_key[rank] = a.key ? a.key[row] : (uint8_t)0xFFu;
         if (rank == a.n - 1u) a.word->last = row + 1u;
     }
     // the tile's byte range of an output, seen from the 16-byte boundary at or before its start

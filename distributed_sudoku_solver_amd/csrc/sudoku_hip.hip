@@ -372,6 +372,7 @@ struct sdk_ctx {
     DevBuf gr_in;                  // sdk_grade_batch_dev with d_out == d_in: a slice's inputs
     DevBuf gr_level, gr_open;      // sdk_grade_batch: the host-pointer call's grades (gr_open also
                                    // where the caller wants no open counts)
+    DevBuf rt_bd, rt_key;          // sdk_rate_batch: the host-pointer call's ratings
     int64_t gen_cap = 1 << 20;     // SDK_OPT_GEN_CAP: a generated grid is kept iff its fill placed at most this many digits
     DevBuf gen_order;              // sdk_generate_puzzles: a slice's removal orders
     DevBuf gen_plc;                // sdk_generate_grids (host pointers): the placement counts
@@ -380,6 +381,7 @@ struct sdk_ctx {
     // ballot, popcount, offset); the call's device word (sdk::SelWord); the host-pointer call's outputs
     DevBuf gg_puz, gg_grid, gg_st, gg_sol, gg_gst, gg_level, gg_open, gg_ballot, gg_count, gg_offset, gg_word;
     DevBuf gg_out_puz, gg_out_grid, gg_out_level, gg_out_open, gg_out_index;
+    DevBuf gg_bd, gg_key, gg_out_bd, gg_out_key;   // sdk_generate_rated: a round's ratings, the host call's
     DevBuf fr_a, fr_b, prop, bcell, bmask, nchild, offs, fr_status, fr_mask, tsum, fr_ctl;
     DevBuf fr_tail;                // refine_head: the boards kept after the refined ones
     // the device-resident frontier of the last sdk_frontier_build (in fr_a)
@@ -496,14 +498,14 @@ struct Piece {
 };
 
 // The copies of a host-pointer call: send() before the launch, fetch() after it (it synchronizes).
-// The (at most five) pieces lie in the pinned area (HostBuf) in the order given -- widest element
+// The (at most seven) pieces lie in the pinned area (HostBuf) in the order given -- widest element
 // type first, so every slot is aligned for its type; a call too large for the area copies straight
 // from / to the caller's pageable memory.  An error return between send() and the end of fetch()
 // may leave copies from / into the area queued, so the stream is drained first: the next call's
 // memcpy into the area (or a grow that frees it) cannot race them.
 class Staging {
     sdk_ctx* c;
-    Piece p[5];
+    Piece p[7];
     int np = 0;
     bool armed = true;
 
@@ -1070,8 +1072,14 @@ int launch_classify(sdk_ctx* c, const uint8_t* d_in, uint8_t* d_out, int8_t* d_s
 // copied aside first (the pass and the scatter read a board's input after its group's output is
 // written).  budget as launch_classify's.  Outcome fields as a classify that ran the pass:
 // prop32_ran (SDK_OPT_PROP32_UNDECIDED counts the last slice's listed boards), dn_ran false.
+// d_bd non-null (sdk_rate_batch; rate32_kernel.h): the rate stage, per slice and behind its verdict
+// kernel -- a slice's list is valid only inside its own iteration -- the slice's ratings filled with
+// SDK_RATE_NONE, the dequeue counter (the pass's first control word, idle by then) cleared, and one
+// wave per level-4 board of the list, whose length stays on the device.  The parents are the pass's
+// inputs (the copy put aside when in place), the completions the slice's rows of d_out.  d_key
+// nullable.  Without it the call enqueues exactly what it did before the stage existed.
 int launch_grade(sdk_ctx* c, const uint8_t* d_in, uint8_t* d_out, int8_t* d_status, uint8_t* d_level, uint8_t* d_open,
-                 size_t n, int64_t budget) {
+                 size_t n, int64_t budget, uint8_t* d_bd = nullptr, uint8_t* d_key = nullptr) {
     if (n == 0) return SDK_OK;
     if ((reinterpret_cast<uintptr_t>(d_in) | reinterpret_cast<uintptr_t>(d_out)) & 15u)
         return fail(SDK_EINVAL, "device boards must be 16-byte aligned");
@@ -1106,6 +1114,25 @@ int launch_grade(sdk_ctx* c, const uint8_t* d_in, uint8_t* d_out, int8_t* d_stat
         if (sdk::launch_g32_verdict(a.p.list, static_cast<const int8_t*>(c->p32_st.p), a.level, a.open,
                                     grid_for(c, m, 256, 8), c->stream) != hipSuccess)
             rc = fail(SDK_EHIP, "grade verdict launch failed");
+        if (!rc && d_bd) {
+            sdk::Rate32Args r{};
+            r.in = in;
+            r.sol = a.p.out;
+            r.level = a.level;
+            r.list = a.p.list;
+            r.n = m;
+            r.next = a.p.heads;
+            r.backdoors = d_bd + b0;
+            r.key = d_key ? d_key + b0 : nullptr;
+            r.lc_every = (uint32_t)std::max<int64_t>(1, c->prop32_lc & 0xFF);
+            r.lc_first = (c->prop32_lc >> 8) ? (uint32_t)(c->prop32_lc >> 8) : r.lc_every;
+            HIPCALL(hipMemsetAsync(r.backdoors, 0xFF, m, c->stream));
+            if (r.key) HIPCALL(hipMemsetAsync(r.key, 0xFF, m, c->stream));
+            HIPCALL(hipMemsetAsync(r.next, 0, 4, c->stream));
+            // four waves per SIMD, as the grader; at most one wave per listed board
+            if (sdk::launch_rate32(r, grid_for(c, m, 1, 16), c->stream) != hipSuccess)
+                rc = fail(SDK_EHIP, "rate launch failed");
+        }
     }
     return span.end(rc);
 }
@@ -1234,6 +1261,12 @@ struct GradedCall {
     uint64_t max_scan, chunk;
     uint8_t *puzzles, *grids, *level, *open;
     uint64_t* index;
+    // sdk_generate_rated: a level-4 candidate is a hit only with bd_lo <= backdoors <= bd_hi; a round's
+    // grade then runs the rate stage (skipped when level 4 is not asked for: nothing would be filtered,
+    // and the outputs of levels 1..3 are SDK_RATE_NONE anyway)
+    bool rated = false;
+    uint32_t bd_lo = 0, bd_hi = 64;
+    uint8_t *backdoors = nullptr, *key = nullptr;
 };
 
 int launch_generate_graded(sdk_ctx* c, const GradedCall& g, uint64_t* found, uint64_t* scanned) {
@@ -1274,6 +1307,10 @@ int launch_generate_graded(sdk_ctx* c, const GradedCall& g, uint64_t* found, uin
             (rc = ensure(c->gg_ballot, (size_t)tiles * 8)) || (rc = ensure(c->gg_count, (size_t)tiles * 4)) ||
             (rc = ensure(c->gg_offset, (size_t)tiles * 4)))
             return rc;
+        const bool rate = g.rated && (g.level_mask >> SDK_GRADE_SEARCH & 1u);
+        if (rate && ((rc = ensure(c->gg_bd, rows)) || (rc = ensure(c->gg_key, rows)))) return rc;
+        uint8_t* bd = rate ? static_cast<uint8_t*>(c->gg_bd.p) : nullptr;
+        uint8_t* key = rate ? static_cast<uint8_t*>(c->gg_key.p) : nullptr;
         uint8_t* puz = static_cast<uint8_t*>(c->gg_puz.p);
         uint8_t* grid = static_cast<uint8_t*>(c->gg_grid.p);
         int8_t* st = static_cast<int8_t*>(c->gg_st.p);
@@ -1281,7 +1318,7 @@ int launch_generate_graded(sdk_ctx* c, const GradedCall& g, uint64_t* found, uin
         uint8_t* open = static_cast<uint8_t*>(c->gg_open.p);
         if ((rc = launch_generate_puzzles(c, g.seed, g.first + done, m, puz, grid, st)) ||
             (rc = launch_grade(c, puz, static_cast<uint8_t*>(c->gg_sol.p), static_cast<int8_t*>(c->gg_gst.p), level,
-                               open, m, 0)))
+                               open, m, 0, bd, key)))
             return rc;
         sdk::SelFlagArgs fa{};
         fa.puzzles = puz;
@@ -1291,6 +1328,9 @@ int launch_generate_graded(sdk_ctx* c, const GradedCall& g, uint64_t* found, uin
         fa.level_mask = g.level_mask;
         fa.clues_lo = g.clues_lo;
         fa.clues_hi = g.clues_hi;
+        fa.backdoors = bd;
+        fa.bd_lo = g.bd_lo;
+        fa.bd_hi = g.bd_hi;
         fa.ballot = static_cast<unsigned long long*>(c->gg_ballot.p);
         fa.count = static_cast<uint32_t*>(c->gg_count.p);
         sdk::SelScanArgs sa{};
@@ -1312,6 +1352,10 @@ int launch_generate_graded(sdk_ctx* c, const GradedCall& g, uint64_t* found, uin
         ca.out_level = g.level;
         ca.out_open = g.open;
         ca.out_index = g.index;
+        ca.backdoors = bd;
+        ca.key = key;
+        ca.out_backdoors = g.backdoors;
+        ca.out_key = g.key;
         ca.word = d_word;
         HIPCALL(sdk::launch_select_flag(fa, tiles, c->stream));
         HIPCALL(sdk::launch_select_scan(sa, c->stream));
@@ -1343,6 +1387,12 @@ int check_graded_args(uint64_t first, size_t n, uint32_t level_mask, uint32_t cl
     if (max_scan == 0) return fail(SDK_EINVAL, "max_scan must be at least 1");
     if (first > UINT64_MAX - max_scan) return fail(SDK_EINVAL, "first + max_scan overflows the stream index");
     if (chunk > kGradedChunkMax) return fail(SDK_EINVAL, "chunk must be 0 (automatic) or 1..2^24");
+    return SDK_OK;
+}
+
+// ... and the backdoor range of sdk_generate_rated
+int check_rated_range(uint32_t lo, uint32_t hi) {
+    if (lo > hi || hi > 64) return fail(SDK_EINVAL, "backdoor range must be backdoors_lo <= backdoors_hi <= 64");
     return SDK_OK;
 }
 
@@ -2194,6 +2244,52 @@ int sdk_grade_batch(sdk_ctx* c, const uint8_t* in, uint8_t* out, int8_t* status,
     return io.fetch();
 }
 
+int sdk_rate_batch_dev(sdk_ctx* c, const void* d_in, void* d_out, void* d_status, void* d_level, void* d_open,
+                       void* d_backdoors, void* d_key, size_t n, uint64_t node_budget) {
+    if (!c || (n && (!d_in || !d_out || !d_status || !d_level || !d_backdoors))) return fail(SDK_EINVAL, "NULL argument");
+    int rc;
+    if ((rc = check_budget_arg(node_budget))) return rc;
+    if (n == 0) return SDK_OK;
+    if ((rc = check_board_count(n))) return rc;
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCALL(hipSetDevice(c->device));
+    return launch_grade(c, static_cast<const uint8_t*>(d_in), static_cast<uint8_t*>(d_out),
+                        static_cast<int8_t*>(d_status), static_cast<uint8_t*>(d_level), static_cast<uint8_t*>(d_open),
+                        n, budget_arg(node_budget), static_cast<uint8_t*>(d_backdoors), static_cast<uint8_t*>(d_key));
+}
+
+int sdk_rate_batch(sdk_ctx* c, const uint8_t* in, uint8_t* out, int8_t* status, uint8_t* level, uint8_t* open,
+                   uint8_t* backdoors, uint8_t* key, size_t n, uint64_t node_budget) {
+    if (!c || (n && (!in || !out || !status || !level || !backdoors))) return fail(SDK_EINVAL, "NULL argument");
+    int rc;
+    if ((rc = check_budget_arg(node_budget))) return rc;
+    if (n == 0) return SDK_OK;
+    if ((rc = check_board_count(n))) return rc;
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCALL(hipSetDevice(c->device));
+    if ((rc = ensure(c->in, n * 81)) || (rc = ensure(c->out, n * 81)) || (rc = ensure(c->status, n)) ||
+        (rc = ensure(c->gr_level, n)) || (open && (rc = ensure(c->gr_open, n))) || (rc = ensure(c->rt_bd, n)) ||
+        (key && (rc = ensure(c->rt_key, n))))
+        return rc;
+    uint8_t* d_in = static_cast<uint8_t*>(c->in.p);
+    uint8_t* d_out = static_cast<uint8_t*>(c->out.p);
+    int8_t* d_status = static_cast<int8_t*>(c->status.p);
+    uint8_t* d_level = static_cast<uint8_t*>(c->gr_level.p);
+    uint8_t* d_open = open ? static_cast<uint8_t*>(c->gr_open.p) : nullptr;
+    uint8_t* d_bd = static_cast<uint8_t*>(c->rt_bd.p);
+    uint8_t* d_key = key ? static_cast<uint8_t*>(c->rt_key.p) : nullptr;
+    Staging io(c, {{n * 81, in, d_in, d_out, out},
+                   {n, nullptr, nullptr, d_status, status},
+                   {n, nullptr, nullptr, d_level, level},
+                   {open ? n : 0, nullptr, nullptr, d_open, open},
+                   {n, nullptr, nullptr, d_bd, backdoors},
+                   {key ? n : 0, nullptr, nullptr, d_key, key}});
+    if ((rc = io.send()) ||
+        (rc = launch_grade(c, d_in, d_out, d_status, d_level, d_open, n, budget_arg(node_budget), d_bd, d_key)))
+        return rc;
+    return io.fetch();
+}
+
 int sdk_minimize_batch_dev(sdk_ctx* c, const void* d_in, const void* d_order, void* d_out, void* d_status, size_t n) {
     if (!c || (n && (!d_in || !d_order || !d_out || !d_status))) return fail(SDK_EINVAL, "NULL argument");
     if (n == 0) return SDK_OK;
@@ -2355,6 +2451,84 @@ int sdk_generate_graded(sdk_ctx* c, uint64_t seed, uint64_t first, size_t n, uin
                            {f * 81, nullptr, nullptr, g.grids, grids},
                            {level ? f : 0, nullptr, nullptr, g.level, level},
                            {open ? f : 0, nullptr, nullptr, g.open, open}});
+            if ((rc = io.fetch())) return rc;
+        }
+    }
+    *found = f;
+    if (scanned) *scanned = s;
+    return SDK_OK;
+}
+
+int sdk_generate_rated_dev(sdk_ctx* c, uint64_t seed, uint64_t first, size_t n, uint32_t level_mask,
+                           uint32_t clues_lo, uint32_t clues_hi, uint32_t backdoors_lo, uint32_t backdoors_hi,
+                           uint64_t max_scan, uint64_t chunk, void* d_puzzles, void* d_grids, void* d_level,
+                           void* d_open, void* d_backdoors, void* d_key, void* d_index, uint64_t* found,
+                           uint64_t* scanned) {
+    if (!c || !found || (n && (!d_puzzles || !d_grids))) return fail(SDK_EINVAL, "NULL argument");
+    int rc;
+    if ((rc = check_graded_args(first, n, level_mask, clues_lo, clues_hi, max_scan, chunk)) ||
+        (rc = check_rated_range(backdoors_lo, backdoors_hi)))
+        return rc;
+    if ((reinterpret_cast<uintptr_t>(d_puzzles) | reinterpret_cast<uintptr_t>(d_grids)) & 15u)
+        return fail(SDK_EINVAL, "device boards must be 16-byte aligned");
+    if (reinterpret_cast<uintptr_t>(d_index) & 7u) return fail(SDK_EINVAL, "d_index must be 8-byte aligned");
+    uint64_t f = 0, s = 0;
+    if (n) {
+        std::lock_guard<std::mutex> lk(c->mu);
+        HIPCALL(hipSetDevice(c->device));
+        GradedCall g{seed, first, (uint32_t)n, level_mask, clues_lo, clues_hi, max_scan, chunk,
+                     static_cast<uint8_t*>(d_puzzles), static_cast<uint8_t*>(d_grids), static_cast<uint8_t*>(d_level),
+                     static_cast<uint8_t*>(d_open), static_cast<uint64_t*>(d_index)};
+        g.rated = true;
+        g.bd_lo = backdoors_lo;
+        g.bd_hi = backdoors_hi;
+        g.backdoors = static_cast<uint8_t*>(d_backdoors);
+        g.key = static_cast<uint8_t*>(d_key);
+        if ((rc = launch_generate_graded(c, g, &f, &s))) return rc;
+    }
+    *found = f;
+    if (scanned) *scanned = s;
+    return SDK_OK;
+}
+
+int sdk_generate_rated(sdk_ctx* c, uint64_t seed, uint64_t first, size_t n, uint32_t level_mask, uint32_t clues_lo,
+                       uint32_t clues_hi, uint32_t backdoors_lo, uint32_t backdoors_hi, uint64_t max_scan,
+                       uint64_t chunk, uint8_t* puzzles, uint8_t* grids, uint8_t* level, uint8_t* open,
+                       uint8_t* backdoors, uint8_t* key, uint64_t* index, uint64_t* found, uint64_t* scanned) {
+    if (!c || !found || (n && (!puzzles || !grids))) return fail(SDK_EINVAL, "NULL argument");
+    int rc;
+    if ((rc = check_graded_args(first, n, level_mask, clues_lo, clues_hi, max_scan, chunk)) ||
+        (rc = check_rated_range(backdoors_lo, backdoors_hi)))
+        return rc;
+    uint64_t f = 0, s = 0;
+    if (n) {
+        std::lock_guard<std::mutex> lk(c->mu);
+        HIPCALL(hipSetDevice(c->device));
+        const size_t rows = (size_t)std::min<uint64_t>(n, max_scan);
+        if ((rc = ensure(c->gg_out_puz, rows * 81)) || (rc = ensure(c->gg_out_grid, rows * 81)) ||
+            (level && (rc = ensure(c->gg_out_level, rows))) || (open && (rc = ensure(c->gg_out_open, rows))) ||
+            (backdoors && (rc = ensure(c->gg_out_bd, rows))) || (key && (rc = ensure(c->gg_out_key, rows))) ||
+            (index && (rc = ensure(c->gg_out_index, rows * 8))))
+            return rc;
+        GradedCall g{seed, first, (uint32_t)n, level_mask, clues_lo, clues_hi, max_scan, chunk,
+                     static_cast<uint8_t*>(c->gg_out_puz.p), static_cast<uint8_t*>(c->gg_out_grid.p),
+                     level ? static_cast<uint8_t*>(c->gg_out_level.p) : nullptr,
+                     open ? static_cast<uint8_t*>(c->gg_out_open.p) : nullptr,
+                     index ? static_cast<uint64_t*>(c->gg_out_index.p) : nullptr};
+        g.rated = true;
+        g.bd_lo = backdoors_lo;
+        g.bd_hi = backdoors_hi;
+        g.backdoors = backdoors ? static_cast<uint8_t*>(c->gg_out_bd.p) : nullptr;
+        g.key = key ? static_cast<uint8_t*>(c->gg_out_key.p) : nullptr;
+        if ((rc = launch_generate_graded(c, g, &f, &s))) return rc;
+        if (f) {
+            Staging io(c, {{index ? f * 8 : 0, nullptr, nullptr, g.index, index},
+                           {f * 81, nullptr, nullptr, g.puzzles, puzzles},
+                           {f * 81, nullptr, nullptr, g.grids, grids},
+                           {level ? f : 0, nullptr, nullptr, g.level, level},
+                           {open ? f : 0, nullptr, nullptr, g.open, open},
+                           {backdoors ? f : 0, nullptr, nullptr, g.backdoors, backdoors},
+                           {key ? f : 0, nullptr, nullptr, g.key, key}});
             if ((rc = io.fetch())) return rc;
         }
     }

@@ -323,6 +323,27 @@ class SudokuEngine:
                 "sdk_grade_batch")
         return status, level, open_, out
 
+    def rate_batch(self, boards, budget=None):
+        """uint8[n,81] -> (status int8[n], level uint8[n], open uint8[n], backdoors uint8[n], key
+        uint8[n], out uint8[n,81]): grade_batch, and for every level-4 board its single-cell backdoors
+        (sdk_rate_batch) -- the empty cells whose correct digit, once given, lets the three techniques
+        finish the board.  backdoors is their number (0: the board needs two guesses), key the lowest
+        such cell (SDK_RATE_NONE = 0xFF if none); both are 0xFF for every board of another level.
+        status, level, open and out are exactly grade_batch's.  Like grade_batch this call is not
+        sharded by MultiDeviceEngine or ShardedBatch: it runs on this engine's device."""
+        boards = np.ascontiguousarray(boards, dtype=np.uint8).reshape(-1, 81)
+        n = boards.shape[0]
+        if budget is not None and not 0 <= int(budget) < (1 << 63):
+            raise ValueError("budget must be 0 (unlimited) or a positive node count")
+        out = np.empty_like(boards)
+        status = np.empty(n, dtype=np.int8)
+        level, open_, backdoors, key = (np.empty(n, dtype=np.uint8) for _ in range(4))
+        L.check(self.lib.sdk_rate_batch(self.ctx, _ptr(boards), _ptr(out), _ptr(status), _ptr(level), _ptr(open_),
+                                        _ptr(backdoors), _ptr(key), n,
+                                        L.SDK_BUDGET_CONTEXT if budget is None else int(budget)),
+                "sdk_rate_batch")
+        return status, level, open_, backdoors, key, out
+
     @staticmethod
     def check_order(order, n):
         """order -> uint8[n,81], every row a permutation of 0..80 (else ValueError)."""
@@ -433,6 +454,37 @@ class SudokuEngine:
                 "sdk_generate_graded")
         f = found.value
         return puzzles[:f], grids[:f], level[:f], open_[:f], index[:f], scanned.value
+
+    @staticmethod
+    def _rated_args(n, levels, seed, lo, clues, backdoors, max_scan, chunk):
+        """The arguments of sdk_generate_rated from generate_rated's (ValueError for a bad one)."""
+        seed, lo, n, mask, clues_lo, clues_hi, max_scan, chunk = SudokuEngine._graded_args(
+            n, levels, seed, lo, clues, max_scan, chunk)
+        bd_lo, bd_hi = (0, 64) if backdoors is None else (int(backdoors[0]), int(backdoors[1]))
+        if not 0 <= bd_lo <= bd_hi <= 64:
+            raise ValueError("backdoors must be (lo, hi) with 0 <= lo <= hi <= 64")
+        return seed, lo, n, mask, clues_lo, clues_hi, bd_lo, bd_hi, max_scan, chunk
+
+    def generate_rated(self, n, levels=(1, 2, 3, 4), seed=synth.DEFAULT_SEED + 3, lo=0, clues=None, backdoors=None,
+                       max_scan=1 << 26, chunk=0):
+        """generate_graded with a rating filter (sdk_generate_rated): a level-4 puzzle is kept only when
+        its rate_batch backdoor count lies in backdoors = (lo, hi) (None: 0..64); puzzles of levels 1..3
+        are not filtered by it.  Returns generate_graded's tuple with the ratings after open:
+        (puzzles, solutions, level, open, backdoors uint8[found], key uint8[found], index, scanned);
+        backdoors and key are 0xFF for the puzzles of levels 1..3."""
+        args = self._rated_args(n, levels, seed, lo, clues, backdoors, max_scan, chunk)
+        rows = min(args[2], args[8])
+        puzzles = np.empty((rows, 81), dtype=np.uint8)
+        grids = np.empty((rows, 81), dtype=np.uint8)
+        level, open_, bd, key = (np.empty(rows, dtype=np.uint8) for _ in range(4))
+        index = np.empty(rows, dtype=np.uint64)
+        found, scanned = ctypes.c_uint64(), ctypes.c_uint64()
+        L.check(self.lib.sdk_generate_rated(self.ctx, *args, _ptr(puzzles), _ptr(grids), _ptr(level), _ptr(open_),
+                                            _ptr(bd), _ptr(key), _ptr(index), ctypes.byref(found),
+                                            ctypes.byref(scanned)),
+                "sdk_generate_rated")
+        f = found.value
+        return puzzles[:f], grids[:f], level[:f], open_[:f], bd[:f], key[:f], index[:f], scanned.value
 
     def expand(self, boards, masks=None, target=64):
         """Lex-ordered frontier below `boards` (sdk_expand_boards): uint8[k,81], children in the
@@ -616,6 +668,15 @@ class SudokuEngine:
                                              L.SDK_BUDGET_CONTEXT if budget is None else int(budget)),
                 "sdk_grade_batch_dev")
 
+    def rate_batch_dev(self, d_in, d_out, d_status, d_level, d_backdoors, n, d_open=None, d_key=None, budget=None):
+        """rate_batch on device buffers: as grade_batch_dev (d_in and d_out 16-byte aligned, d_out may
+        be d_in), d_backdoors required, d_open and d_key optional."""
+        L.check(self.lib.sdk_rate_batch_dev(self.ctx, d_in.ptr, d_out.ptr, d_status.ptr, d_level.ptr,
+                                            d_open.ptr if d_open else None, d_backdoors.ptr,
+                                            d_key.ptr if d_key else None, int(n),
+                                            L.SDK_BUDGET_CONTEXT if budget is None else int(budget)),
+                "sdk_rate_batch_dev")
+
     def minimize_batch_dev(self, d_in, d_order, d_out, d_status, n):
         """The order rows are not validated on this path (see include/sudoku_hip.h)."""
         L.check(self.lib.sdk_minimize_batch_dev(self.ctx, d_in.ptr, d_order.ptr, d_out.ptr, d_status.ptr, int(n)),
@@ -644,4 +705,18 @@ class SudokuEngine:
                                                  d_index.ptr if d_index else None, ctypes.byref(found),
                                                  ctypes.byref(scanned)),
                 "sdk_generate_graded_dev")
+        return found.value, scanned.value
+
+    def generate_rated_dev(self, d_puzzles, d_grids, n, levels=(1, 2, 3, 4), seed=synth.DEFAULT_SEED + 3, lo=0,
+                           clues=None, backdoors=None, max_scan=1 << 26, chunk=0, d_level=None, d_open=None,
+                           d_backdoors=None, d_key=None, d_index=None):
+        """generate_rated into device buffers of n rows, as generate_graded_dev: -> (found, scanned)."""
+        args = self._rated_args(n, levels, seed, lo, clues, backdoors, max_scan, chunk)
+        found, scanned = ctypes.c_uint64(), ctypes.c_uint64()
+        L.check(self.lib.sdk_generate_rated_dev(self.ctx, *args, d_puzzles.ptr, d_grids.ptr,
+                                                d_level.ptr if d_level else None, d_open.ptr if d_open else None,
+                                                d_backdoors.ptr if d_backdoors else None,
+                                                d_key.ptr if d_key else None, d_index.ptr if d_index else None,
+                                                ctypes.byref(found), ctypes.byref(scanned)),
+                "sdk_generate_rated_dev")
         return found.value, scanned.value

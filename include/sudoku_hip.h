@@ -14,6 +14,10 @@
  *       -> sdk_check_batch / sdk_check_batch_dev
  *   (no reference counterpart)
  *       -> sdk_count_solutions
+ *   (no reference counterpart: a batch's verdicts, the technique a board needs,
+ *   and inside the search level the number of single-cell backdoors)
+ *       -> sdk_classify_batch, sdk_grade_batch, sdk_rate_batch
+ *       -> sdk_generate_puzzles, sdk_generate_graded, sdk_generate_rated
  *   DFS subtree split across ring nodes (NEEDWORK/TASK, DHT_Node.py:491-510,
  *   225-250; utils.py:1-9) -- within one node of GPUs:
  *       -> sdk_frontier_* + sdk_comm_* (RCCL over xGMI)
@@ -46,6 +50,7 @@ extern "C" {
                             /* also gained sdk_classify_batch[_dev] and sdk_minimize_batch[_dev]  */
                             /* and sdk_generate_grids[_dev] / sdk_generate_puzzles[_dev]          */
                             /* and sdk_grade_batch[_dev] and sdk_generate_graded[_dev]            */
+                            /* and sdk_rate_batch[_dev] and sdk_generate_rated[_dev]              */
                             /* (new symbols only: nothing a version-2 caller uses changed)        */
 
 /* return codes */
@@ -275,6 +280,34 @@ int sdk_classify_batch(sdk_ctx *ctx, const uint8_t *in, uint8_t *out, int8_t *st
 int sdk_grade_batch(sdk_ctx *ctx, const uint8_t *in, uint8_t *out, int8_t *status, uint8_t *level,
                     uint8_t *open, size_t n, uint64_t node_budget);
 
+/* Ratings inside level SDK_GRADE_SEARCH: how many single-cell backdoors does a board have?
+ *
+ * Take a board of level SDK_GRADE_SEARCH: exactly one completion S, clean givens, F_3 not closed.
+ * For an empty input cell c, child(c) is the board with S[c] written into c, and c is a backdoor
+ * when every cell of F_3(child(c)) is closed: the one guess that lets the techniques finish.
+ *   backdoors  uint8[n], required: the number of backdoor cells, 0..64 (a uniquely solvable board
+ *              has at least 17 clues, so at most 64 empty cells).  0: no single right guess is
+ *              enough, the board needs two.
+ *   key        uint8[n], nullable: the lowest-index backdoor cell (0..80), SDK_RATE_NONE if none.
+ * Both are SDK_RATE_NONE for every board of any other level (no probe is run for them), a board
+ * whose search hit the node budget (level SDK_GRADE_NONE) included.
+ * By the monotonicity argument above (the rules only remove, and a rule that can fire stays able
+ * to): F_3 of a child does not depend on the schedule; a child built from the input, from F_3's
+ * closed cells, or from any grid between the two has the same F_3; a cell already closed in F_3 is
+ * never a backdoor (its child has the parent's F_3, which is open), so counting over the empty
+ * cells and over the open cells of F_3 is the same; and a child holds S, so it is never refuted
+ * and its givens are clean.  The rating is a pure function of the board.
+ *   status, out, level, open  exactly sdk_grade_batch's, byte for byte, under every option and
+ *              budget (open nullable).
+ * The call is a grade call with one more stage per slice (rate32_kernel.h: all the probes of one
+ * board are one group of the propagation pass, synthesised in registers -- no child is ever
+ * written to memory).  It changes no option and leaves SDK_OPT_PROP32_UNDECIDED as a grade call
+ * does; its result does not depend on SDK_OPT_PROP32_LC.  Any n up to 2^31-1 (slices of 2^24
+ * boards); one span under SDK_OPT_TIMING. */
+#define SDK_RATE_NONE 0xFFu
+int sdk_rate_batch(sdk_ctx *ctx, const uint8_t *in, uint8_t *out, int8_t *status, uint8_t *level,
+                   uint8_t *open, uint8_t *backdoors, uint8_t *key, size_t n, uint64_t node_budget);
+
 /* Greedy clue removal for n boards.  order is uint8[n][81]; row i is a permutation of 0..80, the
  * cell order in which board i's clues are tried (anything else: SDK_EINVAL).  Per board:
  *   status[i] = sdk_classify_batch's verdict of the input (no budget);
@@ -353,6 +386,24 @@ int sdk_generate_graded(sdk_ctx *ctx, uint64_t seed, uint64_t first, size_t n,
                         uint64_t max_scan, uint64_t chunk,
                         uint8_t *puzzles, uint8_t *grids, uint8_t *level, uint8_t *open,
                         uint64_t *index, uint64_t *found, uint64_t *scanned);
+
+/* Puzzles of a requested grade and rating: sdk_generate_graded with one more condition.  Candidate k
+ * is a hit when it is a hit of sdk_generate_graded(level_mask, clues_lo, clues_hi) and, if its level
+ * is SDK_GRADE_SEARCH, backdoors_lo <= backdoors <= backdoors_hi (sdk_rate_batch's count with no
+ * node budget).  Candidates of levels 1..3 are not filtered by the range.
+ *   backdoors_lo <= backdoors_hi <= 64, else SDK_EINVAL;
+ *   backdoors, key  uint8[n], nullable: the hits' ratings (SDK_RATE_NONE for levels 1..3).
+ * Everything else is sdk_generate_graded's: the window, found, scanned, chunk (speed only), the
+ * purity of the result (now also a function of the range), one 8-byte readback per round, one span.
+ * A round grades with the rate stage; when level_mask lacks SDK_GRADE_SEARCH the stage is skipped.
+ * With the range (0, 64) the shared outputs are sdk_generate_graded's, byte for byte. */
+int sdk_generate_rated(sdk_ctx *ctx, uint64_t seed, uint64_t first, size_t n,
+                       uint32_t level_mask, uint32_t clues_lo, uint32_t clues_hi,
+                       uint32_t backdoors_lo, uint32_t backdoors_hi,
+                       uint64_t max_scan, uint64_t chunk,
+                       uint8_t *puzzles, uint8_t *grids, uint8_t *level, uint8_t *open,
+                       uint8_t *backdoors, uint8_t *key,
+                       uint64_t *index, uint64_t *found, uint64_t *scanned);
 
 /* The worklist step of a resumable lex-first search of a board whose solve hit the
  * budget (distributed_sudoku_solver_amd/search.py; the in-node form of handing a
@@ -509,6 +560,10 @@ int sdk_minimize_batch_dev(sdk_ctx *ctx, const void *d_in, const void *d_order, 
  * d_in (exactly: any other overlap is undefined).  d_level uint8[n], d_open uint8[n] or NULL. */
 int sdk_grade_batch_dev(sdk_ctx *ctx, const void *d_in, void *d_out, void *d_status, void *d_level,
                         void *d_open, size_t n, uint64_t node_budget);
+/* as sdk_grade_batch_dev (alignment, d_out may be d_in: the parents then come from the copy put
+ * aside); d_backdoors uint8[n] required, d_open and d_key uint8[n] or NULL. */
+int sdk_rate_batch_dev(sdk_ctx *ctx, const void *d_in, void *d_out, void *d_status, void *d_level,
+                       void *d_open, void *d_backdoors, void *d_key, size_t n, uint64_t node_budget);
 /* d_grids (and d_order, d_puzzles) 16-byte aligned, else SDK_EINVAL; d_order and d_placements
  * (uint32[n]) nullable.  Spans as the host-pointer forms: one per call. */
 int sdk_generate_grids_dev(sdk_ctx *ctx, uint64_t seed, uint64_t first, size_t n, void *d_grids,
@@ -524,6 +579,14 @@ int sdk_generate_graded_dev(sdk_ctx *ctx, uint64_t seed, uint64_t first, size_t 
                             uint64_t max_scan, uint64_t chunk,
                             void *d_puzzles, void *d_grids, void *d_level, void *d_open,
                             void *d_index, uint64_t *found, uint64_t *scanned);
+/* as sdk_generate_graded_dev; d_backdoors and d_key uint8[n] or NULL */
+int sdk_generate_rated_dev(sdk_ctx *ctx, uint64_t seed, uint64_t first, size_t n,
+                           uint32_t level_mask, uint32_t clues_lo, uint32_t clues_hi,
+                           uint32_t backdoors_lo, uint32_t backdoors_hi,
+                           uint64_t max_scan, uint64_t chunk,
+                           void *d_puzzles, void *d_grids, void *d_level, void *d_open,
+                           void *d_backdoors, void *d_key,
+                           void *d_index, uint64_t *found, uint64_t *scanned);
 
 /* Kernel time accounting (HIP events on the context stream, bracketing every
  * kernel launched by the *_dev / host calls since the last reset).  Only with
