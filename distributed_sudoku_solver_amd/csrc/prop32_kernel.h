@@ -81,6 +81,22 @@ __device__ __forceinline__ uint32_t p32_half_or(uint32_t x) {
     return r[0] | r[1];
 }
 __device__ __forceinline__ uint32_t p32_half_and(uint32_t x) { return ~p32_half_or(~x); }
+// Two words over each half in one chain: the swap first -- of (a, b) it leaves a's rows in the even
+// rows and b's in the odd rows of both registers, so their OR holds a's row 0 | row 1 of each half in
+// the half's even row and b's in its odd row -- then the four rotations once, inside the rows.  The
+// half's OR of a ends in every lane of rows 0 and 2, of b in rows 1 and 3 (p32_mask64x2 reads them).
+// Six VALU ops where two p32_half_or take twelve, and one dependent chain instead of two.  Every lane
+// of the wave must be active; the spare lanes 27..31 (rows 1 and 3 before the swap) are masked by the
+// caller, as for p32_half_or.
+__device__ __forceinline__ uint32_t p32_half_or2(uint32_t a, uint32_t b) {
+    const auto r = __builtin_amdgcn_permlane16_swap(a, b, false, false);
+    uint32_t x = r[0] | r[1];
+    x |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x121, 0xF, 0xF, false);   // row_ror:1
+    x |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x122, 0xF, 0xF, false);   // row_ror:2
+    x |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x124, 0xF, 0xF, false);   // row_ror:4
+    x |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x128, 0xF, 0xF, false);   // row_ror:8
+    return x;
+}
 
 // one v_bitop3_b32 with truth table TT over (S0 = a, S1 = b, S2 = c).  Left to itself the compiler
 // forms three-input ORs as v_or3_b32, which issues at ~0.6x the rate of v_bitop3_b32
@@ -773,6 +789,14 @@ __device__ __forceinline__ uint64_t p32_mask64(uint32_t v) {
     const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)v, 32);
     return (uint64_t)lo | ((uint64_t)hi << 32);
 }
+// the two board masks of a p32_half_or2 word: a's from rows 0 and 2 (lanes 0, 32), b's from rows 1
+// and 3 (lanes 16, 48)
+__device__ __forceinline__ void p32_mask64x2(uint32_t v, uint64_t& a, uint64_t& b) {
+    a = p32_mask64(v);
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)v, 16);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)v, 48);
+    b = (uint64_t)lo | ((uint64_t)hi << 32);
+}
 
 // the next group of 64 boards: the home segment's counter (blockIdx % kP32Heads, one XCD), then
 // the others in turn.  Returns the group index or ~0u.
@@ -885,12 +909,22 @@ __device__ __forceinline__ void p32_group_begin(const Prop32Args& a, const P32La
     G.contra = 0ull;
 }
 
-// The group's steps.  One exit, at the head: a group that ends in a step still runs that step's cells
-// phase (sound propagation; it only tightens what a handed-over board carries), so every path through
-// a step ends in an update of the cell words and they keep one register home (with exits in the middle
-// of the step the register allocator gave the words a second home and copied all 27 out and back on
-// every step).  Two steps per iteration, so the two copies' register homes of the cell words can
-// alternate instead of being copied back at every latch.
+// The group's steps.  A step may return as soon as its verdicts have emptied the group, before its
+// cells phase (prop32_body does; the grading and rating passes' steps run theirs): the results are
+// the same byte for byte, because no board's answer reads that update --
+//   * a solved board's cells phase is a no-op: every cell is closed, so none loses its units' T, and
+//     no unit holds a digit twice, so every candidate left is a hidden single already;
+//   * a refuted board returns its input;
+//   * a board already in G.undec then is inexact (listed with its input) or was declared stuck at a
+//     locked-candidates pass: unchanged by the step before the pass and by the pass, so at a fixpoint
+//     of both (a board's words depend on no other board's), and every update since has left the grid
+//     it is handed over with as it was -- as the skipped one would.
+// A group that a step ends by handing its live boards over (max_steps, the tail) is not at a fixpoint:
+// that step runs its cells phase, and the boards carry its update.  (Until the step loop fitted 96
+// registers an exit inside the step cost the 27 cell words a second register home and a copy of all
+// of them on every step; now it is 15 v_mov on the exit's edge, once per group, and the blocks of
+// the loop keep their instruction counts.)  Two steps per iteration, so the two copies' register
+// homes of the cell words can alternate instead of being copied back at every latch.
 template <class Step>
 __device__ __forceinline__ void p32_run(const P32Group& G, Step&& step) {
     while (G.live != 0ull) {
@@ -916,9 +950,14 @@ __device__ __forceinline__ void p32_decide(const P32Lane& w, const p32_lds_t* ld
     } else {
         p32_unit<false>(w, lds, miss, dup);
     }
-    const uint64_t badw = p32_mask64(p32_half_or(w.act ? (miss | empty) : 0u));
-    const uint64_t allw = p32_mask64(p32_half_and(w.act ? alls : ~0u));
-    const uint64_t sv = allw & ~badw & G.live, ct = badw & G.live;
+    // the verdict pair in one chain: bad = a unit misses a digit or a cell is empty, and "some cell open"
+    // (the complement of the half's AND of alls; the spare lanes masked to the OR identity in both).
+    // The third words stay single reductions: `dup` above (a group's first step) would only take the
+    // place of one of the pair, the same twelve instructions for the three; the change bits of the step
+    // before a locked-candidates pass come after the cells phase, with no second word to share a chain.
+    uint64_t badw, openw;
+    p32_mask64x2(p32_half_or2(w.act ? (miss | empty) : 0u, w.act ? ~alls : 0u), badw, openw);
+    const uint64_t sv = ~(openw | badw) & G.live, ct = badw & G.live;
     G.solved |= sv;
     G.contra |= ct;
     G.live &= ~(sv | ct);

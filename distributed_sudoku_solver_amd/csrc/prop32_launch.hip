@@ -93,14 +93,19 @@ __device__ __forceinline__ void prop32_body(Prop32Args a, uint64_t* stamps) {
             if (st_t4 == ~0u && __builtin_popcountll(G.live) <= 4) st_t4 = it;
             if (st_t1 == ~0u && __builtin_popcountll(G.live) <= 1) st_t1 = it;
 #endif
-            if (G.live != 0ull) {
-                if (a.tail_live && it >= a.tail_step && (uint32_t)__builtin_popcountll(G.live) <= a.tail_live) {
-                    G.undec |= G.live;   // the last few boards go to the search with their propagated grids
-                    G.live = 0ull;
-                } else if (++it >= a.max_steps) {
-                    G.undec |= G.live;
-                    G.live = 0ull;
-                }
+            // the verdicts emptied the group: no cells phase, nothing reads its update (p32_run)
+            if (G.live == 0ull) {
+                __builtin_amdgcn_wave_barrier();
+                return;
+            }
+            // a group ended by one of these hand-offs is not at a fixpoint: it runs the cells phase
+            // below, and its boards are handed over with this step's update
+            if (a.tail_live && it >= a.tail_step && (uint32_t)__builtin_popcountll(G.live) <= a.tail_live) {
+                G.undec |= G.live;   // the last few boards go to the search with their propagated grids
+                G.live = 0ull;
+            } else if (++it >= a.max_steps) {
+                G.undec |= G.live;
+                G.live = 0ull;
             }
             __builtin_amdgcn_wave_barrier();
             // step lc_first and every lc_every-th after it are followed by a locked-candidates pass;
