@@ -35,6 +35,8 @@ SDK_GRADE_MASK_ALL = 0x1E
 SDK_GRADED_CHUNK_MAX = 1 << 24
 # sdk_rate_batch: backdoors / key of a board that is not of level SDK_GRADE_SEARCH, key of one without a backdoor
 SDK_RATE_NONE = 0xFF
+# sdk_subsets_batch: open4 of a board that is not of level SDK_GRADE_SEARCH
+SDK_SUBSETS_NONE = 0xFF
 
 SDK_CHECK_OK = 1
 SDK_CHECK_RAW_NAMEERROR = 2
@@ -126,6 +128,8 @@ SIGNATURES = {
     "sdk_grade_batch_dev": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, ctypes.c_uint64]),
     "sdk_rate_batch": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, ctypes.c_uint64]),
     "sdk_rate_batch_dev": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, ctypes.c_uint64]),
+    "sdk_subsets_batch": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, ctypes.c_uint64]),
+    "sdk_subsets_batch_dev": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, ctypes.c_uint64]),
     "sdk_minimize_batch": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _sz]),
     "sdk_minimize_batch_dev": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _sz]),
     "sdk_generate_grids": (ctypes.c_int, [_vp, ctypes.c_uint64, ctypes.c_uint64, _sz, _vp, _vp, _vp]),
@@ -148,6 +152,14 @@ SIGNATURES = {
                                               ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
                                               ctypes.c_uint64, ctypes.c_uint64, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                               ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]),
+    "sdk_generate_subsets": (ctypes.c_int, [_vp, ctypes.c_uint64, ctypes.c_uint64, _sz, ctypes.c_uint32,
+                                            ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
+                                            ctypes.c_uint64, ctypes.c_uint64, _vp, _vp, _vp, _vp, _vp, _vp,
+                                            ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]),
+    "sdk_generate_subsets_dev": (ctypes.c_int, [_vp, ctypes.c_uint64, ctypes.c_uint64, _sz, ctypes.c_uint32,
+                                                ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
+                                                ctypes.c_uint64, ctypes.c_uint64, _vp, _vp, _vp, _vp, _vp, _vp,
+                                                ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]),
     "sdk_frontier_boards_dev": (ctypes.c_int, [_vp, ctypes.POINTER(_vp), ctypes.POINTER(ctypes.c_uint64)]),
     "sdk_frontier_load_dev": (ctypes.c_int, [_vp, _vp, ctypes.c_uint64]),
     "sdk_frontier_refine_range": (ctypes.c_int, [_vp, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64,

@@ -11,6 +11,7 @@
 #include "rate_args.h"
 #include "select_args.h"
 #include "solve_args.h"
+#include "subsets_args.h"
 
 namespace sdk {
 
@@ -31,6 +32,9 @@ hipError_t launch_g32_verdict(const uint32_t* list, const int8_t* sub_st, uint8_
 
 // rate32_launch.hip: one wave per level-4 board of the grade pass's list (its length is on the device)
 hipError_t launch_rate32(const Rate32Args& a, unsigned grid, hipStream_t stream);
+
+// subsets_launch.hip: one half-wave per level-4 board of the grade pass's list (its length is on the device)
+hipError_t launch_subsets32(const Subsets32Args& a, unsigned grid, hipStream_t stream);
 
 // select_launch.hip: one wave per tile of 64 rows (flag, scatter), one workgroup (scan)
 hipError_t launch_select_flag(const SelFlagArgs& a, uint32_t tiles, hipStream_t stream);

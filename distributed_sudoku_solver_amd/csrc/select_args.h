@@ -1,5 +1,5 @@
 // select_args.h -- arguments of the selection kernels (select_kernel.h, select_launch.hip): the
-// order-preserving compaction of a round of sdk_generate_graded / sdk_generate_rated, shared with its driver in
+// order-preserving compaction of a round of sdk_generate_graded / _rated / _subsets, shared with its driver in
 // sudoku_hip.hip (launch_generate_graded).
 #pragma once
 #include <cstdint>
@@ -30,6 +30,8 @@ struct SelFlagArgs {
     uint32_t level_mask, clues_lo, clues_hi;
     const uint8_t* backdoors;    // [m] rating, nullable (sdk_generate_rated): a level-4 row is a hit only
     uint32_t bd_lo, bd_hi;       // with bd_lo <= backdoors <= bd_hi; rows of other levels are not filtered
+    const uint8_t* open4;        // [m] subsets count, nullable (sdk_generate_subsets): a level-4 row is a hit
+    uint32_t o4_lo, o4_hi;       // only with o4_lo <= open4 <= o4_hi; rows of other levels are not filtered
     unsigned long long* ballot;  // [tiles] bit l = row 64 t + l is a hit
     uint32_t* count;             // [tiles] its popcount
 };
@@ -59,6 +61,8 @@ struct SelScatterArgs {
     const uint8_t* key;
     uint8_t* out_backdoors;      // [n], nullable
     uint8_t* out_key;            // [n], nullable
+    const uint8_t* open4;        // the round's subsets counts, nullable: SDK_SUBSETS_NONE goes out instead
+    uint8_t* out_open4;          // [n], nullable
     SelWord* word;
 };
 

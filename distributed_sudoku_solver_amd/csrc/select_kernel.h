@@ -7,7 +7,8 @@
 //   flag     one wave per tile of 64 consecutive rows.  The tile (5,184 bytes, 16-byte aligned) goes
 //            to LDS in 16-byte pieces; each lane then counts the clues of its own row, evaluates the
 //            predicate (status SDK_SOLVED, bit `level` of the mask, clues_lo <= clues <= clues_hi; with
-//            ratings, sdk_generate_rated: a level-4 row also bd_lo <= backdoors <= bd_hi) and
+//            ratings, sdk_generate_rated: a level-4 row also bd_lo <= backdoors <= bd_hi; with
+//            subsets counts, sdk_generate_subsets: a level-4 row also o4_lo <= open4 <= o4_hi) and
 //            the wave stores its 64-bit ballot and the ballot's popcount.
 //   scan     ONE workgroup loops over the tile counts (a round of 2^24 rows has 262,144 of them): an
 //            exclusive prefix sum that starts at the hits found so far (SelWord::total) and leaves
@@ -58,6 +59,10 @@ __global__ __launch_bounds__(64) void select_flag_kernel(SelFlagArgs a) {
         if (hit && a.backdoors && lv == 4u) {       // rated generation: the search-level rows by their rating
             const uint32_t bd = a.backdoors[row];
             hit = bd >= a.bd_lo && bd <= a.bd_hi;
+        }
+        if (hit && a.open4 && lv == 4u) {           // ... or by what the subsets leave open
+            const uint32_t o4 = a.open4[row];
+            hit = o4 >= a.o4_lo && o4 <= a.o4_hi;
         }
     }
     const unsigned long long b = __ballot(hit);
@@ -114,6 +119,7 @@ __global__ __launch_bounds__(64) void select_scatter_kernel(SelScatterArgs a) {
         if (a.out_index) a.out_index[rank] = a.first + row;
         if (a.out_backdoors) a.out_backdoors[rank] = a.backdoors ? a.backdoors[row] : (uint8_t)0xFFu;
         if (a.out_key) a.out_key[rank] = a.key ? a.key[row] : (uint8_t)0xFFu;
+        if (a.out_open4) a.out_open4[rank] = a.open4 ? a.open4[row] : (uint8_t)0xFFu;
         if (rank == a.n - 1u) a.word->last = row + 1u;
     }
     // the tile's byte range of an output, seen from the 16-byte boundary at or before its start

@@ -382,6 +382,7 @@ struct sdk_ctx {
     DevBuf gg_puz, gg_grid, gg_st, gg_sol, gg_gst, gg_level, gg_open, gg_ballot, gg_count, gg_offset, gg_word;
     DevBuf gg_out_puz, gg_out_grid, gg_out_level, gg_out_open, gg_out_index;
     DevBuf gg_bd, gg_key, gg_out_bd, gg_out_key;   // sdk_generate_rated: a round's ratings, the host call's
+    DevBuf s4_open4, gg_o4, gg_out_o4;   // sdk_subsets_batch (host pointers); sdk_generate_subsets: a round's, the host call's
     DevBuf fr_a, fr_b, prop, bcell, bmask, nchild, offs, fr_status, fr_mask, tsum, fr_ctl;
     DevBuf fr_tail;                // refine_head: the boards kept after the refined ones
     // the device-resident frontier of the last sdk_frontier_build (in fr_a)
@@ -1078,8 +1079,13 @@ int launch_classify(sdk_ctx* c, const uint8_t* d_in, uint8_t* d_out, int8_t* d_s
 // wave per level-4 board of the list, whose length stays on the device.  The parents are the pass's
 // inputs (the copy put aside when in place), the completions the slice's rows of d_out.  d_key
 // nullable.  Without it the call enqueues exactly what it did before the stage existed.
+// d_open4 non-null (sdk_subsets_batch; subsets_kernel.h): the subsets stage, in the same place and over
+// the same work items -- the slice's counts filled with SDK_SUBSETS_NONE, the same counter cleared, one
+// half-wave per level-4 board of the list.  It reads the parents only.  Without the pointer nothing of
+// it is enqueued.
 int launch_grade(sdk_ctx* c, const uint8_t* d_in, uint8_t* d_out, int8_t* d_status, uint8_t* d_level, uint8_t* d_open,
-                 size_t n, int64_t budget, uint8_t* d_bd = nullptr, uint8_t* d_key = nullptr) {
+                 size_t n, int64_t budget, uint8_t* d_bd = nullptr, uint8_t* d_key = nullptr,
+                 uint8_t* d_open4 = nullptr) {
     if (n == 0) return SDK_OK;
     if ((reinterpret_cast<uintptr_t>(d_in) | reinterpret_cast<uintptr_t>(d_out)) & 15u)
         return fail(SDK_EINVAL, "device boards must be 16-byte aligned");
@@ -1132,6 +1138,20 @@ int launch_grade(sdk_ctx* c, const uint8_t* d_in, uint8_t* d_out, int8_t* d_stat
             // four waves per SIMD, as the grader; at most one wave per listed board
             if (sdk::launch_rate32(r, grid_for(c, m, 1, 16), c->stream) != hipSuccess)
                 rc = fail(SDK_EHIP, "rate launch failed");
+        }
+        if (!rc && d_open4) {
+            sdk::Subsets32Args s{};
+            s.in = in;
+            s.level = a.level;
+            s.list = a.p.list;
+            s.n = m;
+            s.next = a.p.heads;
+            s.open4 = d_open4 + b0;
+            HIPCALL(hipMemsetAsync(s.open4, 0xFF, m, c->stream));
+            HIPCALL(hipMemsetAsync(s.next, 0, 4, c->stream));
+            // four waves per SIMD; at most one wave per two listed boards
+            if (sdk::launch_subsets32(s, grid_for(c, m, 2, 16), c->stream) != hipSuccess)
+                rc = fail(SDK_EHIP, "subsets launch failed");
         }
     }
     return span.end(rc);
@@ -1267,6 +1287,10 @@ struct GradedCall {
     bool rated = false;
     uint32_t bd_lo = 0, bd_hi = 64;
     uint8_t *backdoors = nullptr, *key = nullptr;
+    // sdk_generate_subsets: the same with o4_lo <= open4 <= o4_hi and the subsets stage
+    bool subsets = false;
+    uint32_t o4_lo = 0, o4_hi = 64;
+    uint8_t* open4 = nullptr;
 };
 
 int launch_generate_graded(sdk_ctx* c, const GradedCall& g, uint64_t* found, uint64_t* scanned) {
@@ -1311,6 +1335,9 @@ int launch_generate_graded(sdk_ctx* c, const GradedCall& g, uint64_t* found, uin
         if (rate && ((rc = ensure(c->gg_bd, rows)) || (rc = ensure(c->gg_key, rows)))) return rc;
         uint8_t* bd = rate ? static_cast<uint8_t*>(c->gg_bd.p) : nullptr;
         uint8_t* key = rate ? static_cast<uint8_t*>(c->gg_key.p) : nullptr;
+        const bool subsets = g.subsets && (g.level_mask >> SDK_GRADE_SEARCH & 1u);
+        if (subsets && (rc = ensure(c->gg_o4, rows))) return rc;
+        uint8_t* o4 = subsets ? static_cast<uint8_t*>(c->gg_o4.p) : nullptr;
         uint8_t* puz = static_cast<uint8_t*>(c->gg_puz.p);
         uint8_t* grid = static_cast<uint8_t*>(c->gg_grid.p);
         int8_t* st = static_cast<int8_t*>(c->gg_st.p);
@@ -1318,7 +1345,7 @@ int launch_generate_graded(sdk_ctx* c, const GradedCall& g, uint64_t* found, uin
         uint8_t* open = static_cast<uint8_t*>(c->gg_open.p);
         if ((rc = launch_generate_puzzles(c, g.seed, g.first + done, m, puz, grid, st)) ||
             (rc = launch_grade(c, puz, static_cast<uint8_t*>(c->gg_sol.p), static_cast<int8_t*>(c->gg_gst.p), level,
-                               open, m, 0, bd, key)))
+                               open, m, 0, bd, key, o4)))
             return rc;
         sdk::SelFlagArgs fa{};
         fa.puzzles = puz;
@@ -1331,6 +1358,9 @@ int launch_generate_graded(sdk_ctx* c, const GradedCall& g, uint64_t* found, uin
         fa.backdoors = bd;
         fa.bd_lo = g.bd_lo;
         fa.bd_hi = g.bd_hi;
+        fa.open4 = o4;
+        fa.o4_lo = g.o4_lo;
+        fa.o4_hi = g.o4_hi;
         fa.ballot = static_cast<unsigned long long*>(c->gg_ballot.p);
         fa.count = static_cast<uint32_t*>(c->gg_count.p);
         sdk::SelScanArgs sa{};
@@ -1356,6 +1386,8 @@ int launch_generate_graded(sdk_ctx* c, const GradedCall& g, uint64_t* found, uin
         ca.key = key;
         ca.out_backdoors = g.backdoors;
         ca.out_key = g.key;
+        ca.open4 = o4;
+        ca.out_open4 = g.open4;
         ca.word = d_word;
         HIPCALL(sdk::launch_select_flag(fa, tiles, c->stream));
         HIPCALL(sdk::launch_select_scan(sa, c->stream));
@@ -1393,6 +1425,12 @@ int check_graded_args(uint64_t first, size_t n, uint32_t level_mask, uint32_t cl
 // ... and the backdoor range of sdk_generate_rated
 int check_rated_range(uint32_t lo, uint32_t hi) {
     if (lo > hi || hi > 64) return fail(SDK_EINVAL, "backdoor range must be backdoors_lo <= backdoors_hi <= 64");
+    return SDK_OK;
+}
+
+// ... and the open4 range of sdk_generate_subsets
+int check_subsets_range(uint32_t lo, uint32_t hi) {
+    if (lo > hi || hi > 64) return fail(SDK_EINVAL, "open4 range must be open4_lo <= open4_hi <= 64");
     return SDK_OK;
 }
 
@@ -2290,6 +2328,49 @@ int sdk_rate_batch(sdk_ctx* c, const uint8_t* in, uint8_t* out, int8_t* status, 
     return io.fetch();
 }
 
+int sdk_subsets_batch_dev(sdk_ctx* c, const void* d_in, void* d_out, void* d_status, void* d_level, void* d_open,
+                          void* d_open4, size_t n, uint64_t node_budget) {
+    if (!c || (n && (!d_in || !d_out || !d_status || !d_level || !d_open4))) return fail(SDK_EINVAL, "NULL argument");
+    int rc;
+    if ((rc = check_budget_arg(node_budget))) return rc;
+    if (n == 0) return SDK_OK;
+    if ((rc = check_board_count(n))) return rc;
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCALL(hipSetDevice(c->device));
+    return launch_grade(c, static_cast<const uint8_t*>(d_in), static_cast<uint8_t*>(d_out),
+                        static_cast<int8_t*>(d_status), static_cast<uint8_t*>(d_level), static_cast<uint8_t*>(d_open),
+                        n, budget_arg(node_budget), nullptr, nullptr, static_cast<uint8_t*>(d_open4));
+}
+
+int sdk_subsets_batch(sdk_ctx* c, const uint8_t* in, uint8_t* out, int8_t* status, uint8_t* level, uint8_t* open,
+                      uint8_t* open4, size_t n, uint64_t node_budget) {
+    if (!c || (n && (!in || !out || !status || !level || !open4))) return fail(SDK_EINVAL, "NULL argument");
+    int rc;
+    if ((rc = check_budget_arg(node_budget))) return rc;
+    if (n == 0) return SDK_OK;
+    if ((rc = check_board_count(n))) return rc;
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCALL(hipSetDevice(c->device));
+    if ((rc = ensure(c->in, n * 81)) || (rc = ensure(c->out, n * 81)) || (rc = ensure(c->status, n)) ||
+        (rc = ensure(c->gr_level, n)) || (open && (rc = ensure(c->gr_open, n))) || (rc = ensure(c->s4_open4, n)))
+        return rc;
+    uint8_t* d_in = static_cast<uint8_t*>(c->in.p);
+    uint8_t* d_out = static_cast<uint8_t*>(c->out.p);
+    int8_t* d_status = static_cast<int8_t*>(c->status.p);
+    uint8_t* d_level = static_cast<uint8_t*>(c->gr_level.p);
+    uint8_t* d_open = open ? static_cast<uint8_t*>(c->gr_open.p) : nullptr;
+    uint8_t* d_open4 = static_cast<uint8_t*>(c->s4_open4.p);
+    Staging io(c, {{n * 81, in, d_in, d_out, out},
+                   {n, nullptr, nullptr, d_status, status},
+                   {n, nullptr, nullptr, d_level, level},
+                   {open ? n : 0, nullptr, nullptr, d_open, open},
+                   {n, nullptr, nullptr, d_open4, open4}});
+    if ((rc = io.send()) || (rc = launch_grade(c, d_in, d_out, d_status, d_level, d_open, n, budget_arg(node_budget),
+                                               nullptr, nullptr, d_open4)))
+        return rc;
+    return io.fetch();
+}
+
 int sdk_minimize_batch_dev(sdk_ctx* c, const void* d_in, const void* d_order, void* d_out, void* d_status, size_t n) {
     if (!c || (n && (!d_in || !d_order || !d_out || !d_status))) return fail(SDK_EINVAL, "NULL argument");
     if (n == 0) return SDK_OK;
@@ -2529,6 +2610,79 @@ int sdk_generate_rated(sdk_ctx* c, uint64_t seed, uint64_t first, size_t n, uint
                            {open ? f : 0, nullptr, nullptr, g.open, open},
                            {backdoors ? f : 0, nullptr, nullptr, g.backdoors, backdoors},
                            {key ? f : 0, nullptr, nullptr, g.key, key}});
+            if ((rc = io.fetch())) return rc;
+        }
+    }
+    *found = f;
+    if (scanned) *scanned = s;
+    return SDK_OK;
+}
+
+int sdk_generate_subsets_dev(sdk_ctx* c, uint64_t seed, uint64_t first, size_t n, uint32_t level_mask,
+                             uint32_t clues_lo, uint32_t clues_hi, uint32_t open4_lo, uint32_t open4_hi,
+                             uint64_t max_scan, uint64_t chunk, void* d_puzzles, void* d_grids, void* d_level,
+                             void* d_open, void* d_open4, void* d_index, uint64_t* found, uint64_t* scanned) {
+    if (!c || !found || (n && (!d_puzzles || !d_grids))) return fail(SDK_EINVAL, "NULL argument");
+    int rc;
+    if ((rc = check_graded_args(first, n, level_mask, clues_lo, clues_hi, max_scan, chunk)) ||
+        (rc = check_subsets_range(open4_lo, open4_hi)))
+        return rc;
+    if ((reinterpret_cast<uintptr_t>(d_puzzles) | reinterpret_cast<uintptr_t>(d_grids)) & 15u)
+        return fail(SDK_EINVAL, "device boards must be 16-byte aligned");
+    if (reinterpret_cast<uintptr_t>(d_index) & 7u) return fail(SDK_EINVAL, "d_index must be 8-byte aligned");
+    uint64_t f = 0, s = 0;
+    if (n) {
+        std::lock_guard<std::mutex> lk(c->mu);
+        HIPCALL(hipSetDevice(c->device));
+        GradedCall g{seed, first, (uint32_t)n, level_mask, clues_lo, clues_hi, max_scan, chunk,
+                     static_cast<uint8_t*>(d_puzzles), static_cast<uint8_t*>(d_grids), static_cast<uint8_t*>(d_level),
+                     static_cast<uint8_t*>(d_open), static_cast<uint64_t*>(d_index)};
+        g.subsets = true;
+        g.o4_lo = open4_lo;
+        g.o4_hi = open4_hi;
+        g.open4 = static_cast<uint8_t*>(d_open4);
+        if ((rc = launch_generate_graded(c, g, &f, &s))) return rc;
+    }
+    *found = f;
+    if (scanned) *scanned = s;
+    return SDK_OK;
+}
+
+int sdk_generate_subsets(sdk_ctx* c, uint64_t seed, uint64_t first, size_t n, uint32_t level_mask, uint32_t clues_lo,
+                         uint32_t clues_hi, uint32_t open4_lo, uint32_t open4_hi, uint64_t max_scan, uint64_t chunk,
+                         uint8_t* puzzles, uint8_t* grids, uint8_t* level, uint8_t* open, uint8_t* open4,
+                         uint64_t* index, uint64_t* found, uint64_t* scanned) {
+    if (!c || !found || (n && (!puzzles || !grids))) return fail(SDK_EINVAL, "NULL argument");
+    int rc;
+    if ((rc = check_graded_args(first, n, level_mask, clues_lo, clues_hi, max_scan, chunk)) ||
+        (rc = check_subsets_range(open4_lo, open4_hi)))
+        return rc;
+    uint64_t f = 0, s = 0;
+    if (n) {
+        std::lock_guard<std::mutex> lk(c->mu);
+        HIPCALL(hipSetDevice(c->device));
+        const size_t rows = (size_t)std::min<uint64_t>(n, max_scan);
+        if ((rc = ensure(c->gg_out_puz, rows * 81)) || (rc = ensure(c->gg_out_grid, rows * 81)) ||
+            (level && (rc = ensure(c->gg_out_level, rows))) || (open && (rc = ensure(c->gg_out_open, rows))) ||
+            (open4 && (rc = ensure(c->gg_out_o4, rows))) || (index && (rc = ensure(c->gg_out_index, rows * 8))))
+            return rc;
+        GradedCall g{seed, first, (uint32_t)n, level_mask, clues_lo, clues_hi, max_scan, chunk,
+                     static_cast<uint8_t*>(c->gg_out_puz.p), static_cast<uint8_t*>(c->gg_out_grid.p),
+                     level ? static_cast<uint8_t*>(c->gg_out_level.p) : nullptr,
+                     open ? static_cast<uint8_t*>(c->gg_out_open.p) : nullptr,
+                     index ? static_cast<uint64_t*>(c->gg_out_index.p) : nullptr};
+        g.subsets = true;
+        g.o4_lo = open4_lo;
+        g.o4_hi = open4_hi;
+        g.open4 = open4 ? static_cast<uint8_t*>(c->gg_out_o4.p) : nullptr;
+        if ((rc = launch_generate_graded(c, g, &f, &s))) return rc;
+        if (f) {
+            Staging io(c, {{index ? f * 8 : 0, nullptr, nullptr, g.index, index},
+                           {f * 81, nullptr, nullptr, g.puzzles, puzzles},
+                           {f * 81, nullptr, nullptr, g.grids, grids},
+                           {level ? f : 0, nullptr, nullptr, g.level, level},
+                           {open ? f : 0, nullptr, nullptr, g.open, open},
+                           {open4 ? f : 0, nullptr, nullptr, g.open4, open4}});
             if ((rc = io.fetch())) return rc;
         }
     }

@@ -344,6 +344,26 @@ class SudokuEngine:
                 "sdk_rate_batch")
         return status, level, open_, backdoors, key, out
 
+    def subsets_batch(self, boards, budget=None):
+        """uint8[n,81] -> (status int8[n], level uint8[n], open uint8[n], open4 uint8[n], out
+        uint8[n,81]): grade_batch, and for every level-4 board the number of cells still open once
+        naked and hidden pairs, triples and quads join the three techniques (sdk_subsets_batch).
+        open4 == 0: the subsets finish the board, it needs no guess; open4 is SDK_SUBSETS_NONE = 0xFF
+        for every board of another level.  status, level, open and out are exactly grade_batch's.
+        Like grade_batch and rate_batch this call is not sharded by MultiDeviceEngine or ShardedBatch:
+        it runs on this engine's device."""
+        boards = np.ascontiguousarray(boards, dtype=np.uint8).reshape(-1, 81)
+        n = boards.shape[0]
+        if budget is not None and not 0 <= int(budget) < (1 << 63):
+            raise ValueError("budget must be 0 (unlimited) or a positive node count")
+        out = np.empty_like(boards)
+        status = np.empty(n, dtype=np.int8)
+        level, open_, open4 = (np.empty(n, dtype=np.uint8) for _ in range(3))
+        L.check(self.lib.sdk_subsets_batch(self.ctx, _ptr(boards), _ptr(out), _ptr(status), _ptr(level), _ptr(open_),
+                                           _ptr(open4), n, L.SDK_BUDGET_CONTEXT if budget is None else int(budget)),
+                "sdk_subsets_batch")
+        return status, level, open_, open4, out
+
     @staticmethod
     def check_order(order, n):
         """order -> uint8[n,81], every row a permutation of 0..80 (else ValueError)."""
@@ -485,6 +505,37 @@ class SudokuEngine:
                 "sdk_generate_rated")
         f = found.value
         return puzzles[:f], grids[:f], level[:f], open_[:f], bd[:f], key[:f], index[:f], scanned.value
+
+    @staticmethod
+    def _subsets_args(n, levels, seed, lo, clues, open4, max_scan, chunk):
+        """The arguments of sdk_generate_subsets from generate_subsets's (ValueError for a bad one)."""
+        seed, lo, n, mask, clues_lo, clues_hi, max_scan, chunk = SudokuEngine._graded_args(
+            n, levels, seed, lo, clues, max_scan, chunk)
+        o4_lo, o4_hi = (0, 64) if open4 is None else (int(open4[0]), int(open4[1]))
+        if not 0 <= o4_lo <= o4_hi <= 64:
+            raise ValueError("open4 must be (lo, hi) with 0 <= lo <= hi <= 64")
+        return seed, lo, n, mask, clues_lo, clues_hi, o4_lo, o4_hi, max_scan, chunk
+
+    def generate_subsets(self, n, levels=(1, 2, 3, 4), seed=synth.DEFAULT_SEED + 3, lo=0, clues=None, open4=None,
+                         max_scan=1 << 26, chunk=0):
+        """generate_graded with a subsets filter (sdk_generate_subsets): a level-4 puzzle is kept only
+        when its subsets_batch count lies in open4 = (lo, hi) (None: 0..64); puzzles of levels 1..3 are
+        not filtered by it.  levels=(4,), open4=(0, 0): the hard puzzles that need no guess.  Returns
+        generate_graded's tuple with the counts after open: (puzzles, solutions, level, open, open4
+        uint8[found], index, scanned); open4 is 0xFF for the puzzles of levels 1..3.  Not sharded by
+        MultiDeviceEngine, like generate_graded and generate_rated."""
+        args = self._subsets_args(n, levels, seed, lo, clues, open4, max_scan, chunk)
+        rows = min(args[2], args[8])
+        puzzles = np.empty((rows, 81), dtype=np.uint8)
+        grids = np.empty((rows, 81), dtype=np.uint8)
+        level, open_, o4 = (np.empty(rows, dtype=np.uint8) for _ in range(3))
+        index = np.empty(rows, dtype=np.uint64)
+        found, scanned = ctypes.c_uint64(), ctypes.c_uint64()
+        L.check(self.lib.sdk_generate_subsets(self.ctx, *args, _ptr(puzzles), _ptr(grids), _ptr(level), _ptr(open_),
+                                              _ptr(o4), _ptr(index), ctypes.byref(found), ctypes.byref(scanned)),
+                "sdk_generate_subsets")
+        f = found.value
+        return puzzles[:f], grids[:f], level[:f], open_[:f], o4[:f], index[:f], scanned.value
 
     def expand(self, boards, masks=None, target=64):
         """Lex-ordered frontier below `boards` (sdk_expand_boards): uint8[k,81], children in the
@@ -677,6 +728,14 @@ class SudokuEngine:
                                             L.SDK_BUDGET_CONTEXT if budget is None else int(budget)),
                 "sdk_rate_batch_dev")
 
+    def subsets_batch_dev(self, d_in, d_out, d_status, d_level, d_open4, n, d_open=None, budget=None):
+        """subsets_batch on device buffers: as grade_batch_dev (d_in and d_out 16-byte aligned, d_out
+        may be d_in), d_open4 required, d_open optional."""
+        L.check(self.lib.sdk_subsets_batch_dev(self.ctx, d_in.ptr, d_out.ptr, d_status.ptr, d_level.ptr,
+                                               d_open.ptr if d_open else None, d_open4.ptr, int(n),
+                                               L.SDK_BUDGET_CONTEXT if budget is None else int(budget)),
+                "sdk_subsets_batch_dev")
+
     def minimize_batch_dev(self, d_in, d_order, d_out, d_status, n):
         """The order rows are not validated on this path (see include/sudoku_hip.h)."""
         L.check(self.lib.sdk_minimize_batch_dev(self.ctx, d_in.ptr, d_order.ptr, d_out.ptr, d_status.ptr, int(n)),
@@ -719,4 +778,18 @@ class SudokuEngine:
                                                 d_key.ptr if d_key else None, d_index.ptr if d_index else None,
                                                 ctypes.byref(found), ctypes.byref(scanned)),
                 "sdk_generate_rated_dev")
+        return found.value, scanned.value
+
+    def generate_subsets_dev(self, d_puzzles, d_grids, n, levels=(1, 2, 3, 4), seed=synth.DEFAULT_SEED + 3, lo=0,
+                             clues=None, open4=None, max_scan=1 << 26, chunk=0, d_level=None, d_open=None,
+                             d_open4=None, d_index=None):
+        """generate_subsets into device buffers of n rows, as generate_graded_dev: -> (found, scanned)."""
+        args = self._subsets_args(n, levels, seed, lo, clues, open4, max_scan, chunk)
+        found, scanned = ctypes.c_uint64(), ctypes.c_uint64()
+        L.check(self.lib.sdk_generate_subsets_dev(self.ctx, *args, d_puzzles.ptr, d_grids.ptr,
+                                                  d_level.ptr if d_level else None, d_open.ptr if d_open else None,
+                                                  d_open4.ptr if d_open4 else None,
+                                                  d_index.ptr if d_index else None, ctypes.byref(found),
+                                                  ctypes.byref(scanned)),
+                "sdk_generate_subsets_dev")
         return found.value, scanned.value

@@ -16,8 +16,9 @@
  *       -> sdk_count_solutions
  *   (no reference counterpart: a batch's verdicts, the technique a board needs,
  *   and inside the search level the number of single-cell backdoors)
- *       -> sdk_classify_batch, sdk_grade_batch, sdk_rate_batch
- *       -> sdk_generate_puzzles, sdk_generate_graded, sdk_generate_rated
+ *       -> sdk_classify_batch, sdk_grade_batch, sdk_rate_batch, sdk_subsets_batch
+ *       -> sdk_generate_puzzles, sdk_generate_graded, sdk_generate_rated,
+ *          sdk_generate_subsets
  *   DFS subtree split across ring nodes (NEEDWORK/TASK, DHT_Node.py:491-510,
  *   225-250; utils.py:1-9) -- within one node of GPUs:
  *       -> sdk_frontier_* + sdk_comm_* (RCCL over xGMI)
@@ -51,6 +52,7 @@ extern "C" {
                             /* and sdk_generate_grids[_dev] / sdk_generate_puzzles[_dev]          */
                             /* and sdk_grade_batch[_dev] and sdk_generate_graded[_dev]            */
                             /* and sdk_rate_batch[_dev] and sdk_generate_rated[_dev]              */
+                            /* and sdk_subsets_batch[_dev] and sdk_generate_subsets[_dev]         */
                             /* (new symbols only: nothing a version-2 caller uses changed)        */
 
 /* return codes */
@@ -308,6 +310,31 @@ int sdk_grade_batch(sdk_ctx *ctx, const uint8_t *in, uint8_t *out, int8_t *statu
 int sdk_rate_batch(sdk_ctx *ctx, const uint8_t *in, uint8_t *out, int8_t *status, uint8_t *level,
                    uint8_t *open, uint8_t *backdoors, uint8_t *key, size_t n, uint64_t node_budget);
 
+/* Subsets inside level SDK_GRADE_SEARCH: what do naked and hidden pairs, triples and quads leave open?
+ *
+ * Two more rules on the candidate sets and 27 units of N, H and L (sdk_grade_batch):
+ *   naked S_k   k cells of a unit whose candidate sets have a union of at most k digits: every other
+ *               cell of the unit loses those digits;
+ *   hidden S_k  k digits that only k or fewer cells of a unit hold: those cells lose every other digit.
+ * k = 1 of each is N and H.  R4 = R3 + {naked and hidden S_2, S_3, S_4}, and F_4 is its fixpoint.  Both
+ * premises survive further removals and neither rule removes a digit of a completion, so the argument
+ * above carries over: F_4 is one state whatever the order of application, a pure function of the
+ * board.  A naked subset of k among a unit's m open cells removes what the hidden subset of the other
+ * m - k digits removes; with m <= 9, sizes up to 4 on both sides cover every size.
+ *   open4   uint8[n], required.  For a board of level SDK_GRADE_SEARCH the number of open cells of
+ *           F_4, 0..64; 0: the subsets finish the board, no guess is needed.  SDK_SUBSETS_NONE for
+ *           every board of any other level, a board whose search hit the node budget (level
+ *           SDK_GRADE_NONE) included.
+ *   status, out, level, open  exactly sdk_grade_batch's, byte for byte, under every option and
+ *           budget (open nullable).
+ * The call is a grade call with one more stage per slice (subsets_kernel.h: one level-4 board per
+ * half-wave, one unit per lane, from the board's input row).  It changes no option and leaves
+ * SDK_OPT_PROP32_UNDECIDED as a grade call does.  Any n up to 2^31-1 (slices of 2^24 boards); one span
+ * under SDK_OPT_TIMING. */
+#define SDK_SUBSETS_NONE 0xFFu
+int sdk_subsets_batch(sdk_ctx *ctx, const uint8_t *in, uint8_t *out, int8_t *status, uint8_t *level,
+                      uint8_t *open, uint8_t *open4, size_t n, uint64_t node_budget);
+
 /* Greedy clue removal for n boards.  order is uint8[n][81]; row i is a permutation of 0..80, the
  * cell order in which board i's clues are tried (anything else: SDK_EINVAL).  Per board:
  *   status[i] = sdk_classify_batch's verdict of the input (no budget);
@@ -404,6 +431,25 @@ int sdk_generate_rated(sdk_ctx *ctx, uint64_t seed, uint64_t first, size_t n,
                        uint8_t *puzzles, uint8_t *grids, uint8_t *level, uint8_t *open,
                        uint8_t *backdoors, uint8_t *key,
                        uint64_t *index, uint64_t *found, uint64_t *scanned);
+
+/* Puzzles of a requested grade and subsets count: sdk_generate_graded with one more condition.
+ * Candidate k is a hit when it is a hit of sdk_generate_graded(level_mask, clues_lo, clues_hi) and, if
+ * its level is SDK_GRADE_SEARCH, open4_lo <= open4 <= open4_hi (sdk_subsets_batch's count with no node
+ * budget).  Candidates of levels 1..3 are not filtered by the range.  (0, 0) with level_mask =
+ * 1 << SDK_GRADE_SEARCH: the puzzles beyond locked candidates that need no guess.
+ *   open4_lo <= open4_hi <= 64, else SDK_EINVAL;
+ *   open4  uint8[n], nullable: the hits' counts (SDK_SUBSETS_NONE for levels 1..3).
+ * Everything else is sdk_generate_graded's: the window, found, scanned, chunk (speed only), the
+ * purity of the result (now also a function of the range), one 8-byte readback per round, one span.
+ * A round grades with the subsets stage; when level_mask lacks SDK_GRADE_SEARCH the stage is skipped.
+ * With the range (0, 64) the shared outputs are sdk_generate_graded's, byte for byte. */
+int sdk_generate_subsets(sdk_ctx *ctx, uint64_t seed, uint64_t first, size_t n,
+                         uint32_t level_mask, uint32_t clues_lo, uint32_t clues_hi,
+                         uint32_t open4_lo, uint32_t open4_hi,
+                         uint64_t max_scan, uint64_t chunk,
+                         uint8_t *puzzles, uint8_t *grids, uint8_t *level, uint8_t *open,
+                         uint8_t *open4,
+                         uint64_t *index, uint64_t *found, uint64_t *scanned);
 
 /* The worklist step of a resumable lex-first search of a board whose solve hit the
  * budget (distributed_sudoku_solver_amd/search.py; the in-node form of handing a
@@ -564,6 +610,10 @@ int sdk_grade_batch_dev(sdk_ctx *ctx, const void *d_in, void *d_out, void *d_sta
  * aside); d_backdoors uint8[n] required, d_open and d_key uint8[n] or NULL. */
 int sdk_rate_batch_dev(sdk_ctx *ctx, const void *d_in, void *d_out, void *d_status, void *d_level,
                        void *d_open, void *d_backdoors, void *d_key, size_t n, uint64_t node_budget);
+/* as sdk_grade_batch_dev (alignment, d_out may be d_in); d_open4 uint8[n] required, d_open uint8[n]
+ * or NULL. */
+int sdk_subsets_batch_dev(sdk_ctx *ctx, const void *d_in, void *d_out, void *d_status, void *d_level,
+                          void *d_open, void *d_open4, size_t n, uint64_t node_budget);
 /* d_grids (and d_order, d_puzzles) 16-byte aligned, else SDK_EINVAL; d_order and d_placements
  * (uint32[n]) nullable.  Spans as the host-pointer forms: one per call. */
 int sdk_generate_grids_dev(sdk_ctx *ctx, uint64_t seed, uint64_t first, size_t n, void *d_grids,
@@ -587,6 +637,14 @@ int sdk_generate_rated_dev(sdk_ctx *ctx, uint64_t seed, uint64_t first, size_t n
                            void *d_puzzles, void *d_grids, void *d_level, void *d_open,
                            void *d_backdoors, void *d_key,
                            void *d_index, uint64_t *found, uint64_t *scanned);
+/* as sdk_generate_graded_dev; d_open4 uint8[n] or NULL */
+int sdk_generate_subsets_dev(sdk_ctx *ctx, uint64_t seed, uint64_t first, size_t n,
+                             uint32_t level_mask, uint32_t clues_lo, uint32_t clues_hi,
+                             uint32_t open4_lo, uint32_t open4_hi,
+                             uint64_t max_scan, uint64_t chunk,
+                             void *d_puzzles, void *d_grids, void *d_level, void *d_open,
+                             void *d_open4,
+                             void *d_index, uint64_t *found, uint64_t *scanned);
 
 /* Kernel time accounting (HIP events on the context stream, bracketing every
  * kernel launched by the *_dev / host calls since the last reset).  Only with
