@@ -132,6 +132,11 @@ SIGNATURES = {
     "sdk_subsets_batch_dev": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, ctypes.c_uint64]),
     "sdk_minimize_batch": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _sz]),
     "sdk_minimize_batch_dev": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _sz]),
+    "sdk_minimize_level_batch": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, _vp, _vp, _sz]),
+    "sdk_minimize_level_batch_dev": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, _vp, _vp, _sz]),
+    "sdk_generate_level": (ctypes.c_int, [_vp, ctypes.c_uint64, ctypes.c_uint64, _sz, ctypes.c_int, _vp, _vp, _vp]),
+    "sdk_generate_level_dev": (ctypes.c_int, [_vp, ctypes.c_uint64, ctypes.c_uint64, _sz, ctypes.c_int, _vp, _vp,
+                                              _vp]),
     "sdk_generate_grids": (ctypes.c_int, [_vp, ctypes.c_uint64, ctypes.c_uint64, _sz, _vp, _vp, _vp]),
     "sdk_generate_grids_dev": (ctypes.c_int, [_vp, ctypes.c_uint64, ctypes.c_uint64, _sz, _vp, _vp, _vp]),
     "sdk_generate_puzzles": (ctypes.c_int, [_vp, ctypes.c_uint64, ctypes.c_uint64, _sz, _vp, _vp, _vp]),

@@ -9,6 +9,7 @@
 #include "frontier_args.h"
 #include "prop32_args.h"
 #include "rate_args.h"
+#include "reduce_args.h"
 #include "select_args.h"
 #include "solve_args.h"
 #include "subsets_args.h"
@@ -32,6 +33,9 @@ hipError_t launch_g32_verdict(const uint32_t* list, const int8_t* sub_st, uint8_
 
 // rate32_launch.hip: one wave per level-4 board of the grade pass's list (its length is on the device)
 hipError_t launch_rate32(const Rate32Args& a, unsigned grid, hipStream_t stream);
+
+// reduce32_launch.hip: one wave per group of 64 boards (a.p.heads zeroed), all 81 rounds inside
+hipError_t launch_reduce32(const Reduce32Args& a, unsigned grid, hipStream_t stream);
 
 // subsets_launch.hip: one half-wave per level-4 board of the grade pass's list (its length is on the device)
 hipError_t launch_subsets32(const Subsets32Args& a, unsigned grid, hipStream_t stream);

@@ -91,6 +91,19 @@ int check_board_count(size_t n) {
     if (n > 0x7FFFFFFFull) return fail(SDK_EINVAL, "at most 2^31-1 boards per call");
     return SDK_OK;
 }
+// every row of a host-pointer call's removal orders is a permutation of 0..80
+int check_order_rows(const uint8_t* order, size_t n) {
+    for (size_t i = 0; i < n; ++i) {
+        bool seen[81] = {};
+        for (int q = 0; q < 81; ++q) {
+            const uint8_t v = order[i * 81 + q];
+            if (v >= 81 || seen[v])
+                return fail(SDK_EINVAL, "order row %zu is not a permutation of 0..80 (entry %d = %u)", i, q, (unsigned)v);
+            seen[v] = true;
+        }
+    }
+    return SDK_OK;
+}
 // an ABI node budget as a SolveCall's: SDK_BUDGET_CONTEXT is "the context's"
 int64_t budget_arg(uint64_t node_budget) { return node_budget == SDK_BUDGET_CONTEXT ? -1 : (int64_t)node_budget; }
 
@@ -1249,6 +1262,67 @@ int launch_generate_puzzles(sdk_ctx* c, uint64_t seed, uint64_t first, size_t n,
     return span.end(rc);
 }
 
+// Level-minimal clue removal (sdk_minimize_level_batch; reduce32_kernel.h): per slice of kDnCapBoards
+// boards the pass's dequeue counters cleared and ONE launch -- a group's eligibility run and its 81
+// rounds are inside the kernel.  A group reads its own 64 input rows only (at its begin, and those of
+// its ineligible boards at its end, before it writes) and writes only its own rows, so d_out may be
+// d_in with nothing put aside.  One span under SDK_OPT_TIMING.
+int launch_reduce_level(sdk_ctx* c, const uint8_t* d_in, const uint8_t* d_order, int level, uint8_t* d_out,
+                        int8_t* d_status, size_t n) {
+    if (n == 0) return SDK_OK;
+    if ((reinterpret_cast<uintptr_t>(d_in) | reinterpret_cast<uintptr_t>(d_out)) & 15u)
+        return fail(SDK_EINVAL, "device boards must be 16-byte aligned");
+    int rc;
+    if ((rc = ensure(c->p32_ctl, kCtlBytes))) return rc;
+    TimedSpan span(c);
+    if ((rc = span.begin())) return rc;
+    for (uint64_t b0 = 0; b0 < n; b0 += kDnCapBoards) {
+        const uint64_t m = std::min<uint64_t>(n - b0, kDnCapBoards);
+        sdk::Reduce32Args a{};
+        a.p.in = d_in + b0 * 81;
+        a.p.out = d_out + b0 * 81;
+        a.p.n = m;
+        a.p.heads = static_cast<uint32_t*>(c->p32_ctl.p);
+        a.order = d_order + b0 * 81;
+        a.status = d_status + b0;
+        a.level = (uint32_t)level;
+        HIPCALL(hipMemsetAsync(c->p32_ctl.p, 0, kCtlBytes, c->stream));
+        // three waves per SIMD (reduce32_kernel's registers), one wave per group of 64 boards
+        if (sdk::launch_reduce32(a, grid_for(c, m, 64, 12), c->stream) != hipSuccess) {
+            rc = fail(SDK_EHIP, "level minimise launch failed");
+            break;
+        }
+    }
+    return span.end(rc);
+}
+
+// Level-minimal puzzles (sdk_generate_level): per slice of kDnCapBoards rows, the grids and their
+// removal orders (into the context's gen_order), then the level minimiser over them -- as
+// launch_generate_puzzles with the other minimiser.  One span under SDK_OPT_TIMING.
+int launch_generate_level(sdk_ctx* c, uint64_t seed, uint64_t first, size_t n, int level, uint8_t* d_puzzles,
+                          uint8_t* d_grids, int8_t* d_status) {
+    if (n == 0) return SDK_OK;
+    if ((reinterpret_cast<uintptr_t>(d_puzzles) | reinterpret_cast<uintptr_t>(d_grids)) & 15u)
+        return fail(SDK_EINVAL, "device boards must be 16-byte aligned");
+    int rc;
+    if ((rc = ensure(c->gen_order, std::min<uint64_t>(n, kDnCapBoards) * 81))) return rc;
+    uint8_t* d_order = static_cast<uint8_t*>(c->gen_order.p);
+    TimedSpan span(c);
+    if ((rc = span.begin())) return rc;
+    for (uint64_t b0 = 0; b0 < n && !rc; b0 += kDnCapBoards) {
+        const uint64_t m = std::min<uint64_t>(n - b0, kDnCapBoards);
+        if ((rc = launch_generate(c, seed, first + b0, m, d_grids + b0 * 81, d_order, nullptr))) break;
+        rc = launch_reduce_level(c, d_grids + b0 * 81, d_order, level, d_puzzles + b0 * 81, d_status + b0, m);
+    }
+    return span.end(rc);
+}
+
+int check_level_arg(int level) {
+    if (level < SDK_GRADE_NAKED || level > SDK_GRADE_LOCKED)
+        return fail(SDK_EINVAL, "level must be SDK_GRADE_NAKED..SDK_GRADE_LOCKED (1..3), got %d", level);
+    return SDK_OK;
+}
+
 // argument checks of the four generate calls
 int check_generate_args(uint64_t first, size_t n) {
     int rc;
@@ -2387,16 +2461,7 @@ int sdk_minimize_batch(sdk_ctx* c, const uint8_t* in, const uint8_t* order, uint
     if (n == 0) return SDK_OK;
     int rc;
     if ((rc = check_board_count(n))) return rc;
-    // every order row is a permutation of 0..80
-    for (size_t i = 0; i < n; ++i) {
-        bool seen[81] = {};
-        for (int q = 0; q < 81; ++q) {
-            const uint8_t v = order[i * 81 + q];
-            if (v >= 81 || seen[v])
-                return fail(SDK_EINVAL, "order row %zu is not a permutation of 0..80 (entry %d = %u)", i, q, (unsigned)v);
-            seen[v] = true;
-        }
-    }
+    if ((rc = check_order_rows(order, n))) return rc;
     std::lock_guard<std::mutex> lk(c->mu);
     HIPCALL(hipSetDevice(c->device));
     if ((rc = ensure(c->in, n * 81)) || (rc = ensure(c->mz_order, n * 81)) || (rc = ensure(c->out, n * 81)) ||
@@ -2475,6 +2540,70 @@ int sdk_generate_puzzles(sdk_ctx* c, uint64_t seed, uint64_t first, size_t n, ui
                    {n * 81, nullptr, nullptr, d_grids, grids},
                    {n, nullptr, nullptr, d_status, status}});
     if ((rc = launch_generate_puzzles(c, seed, first, n, d_puzzles, d_grids, d_status))) return rc;
+    return io.fetch();
+}
+
+int sdk_minimize_level_batch_dev(sdk_ctx* c, const void* d_in, const void* d_order, int level, void* d_out,
+                                 void* d_status, size_t n) {
+    if (!c || (n && (!d_in || !d_order || !d_out || !d_status))) return fail(SDK_EINVAL, "NULL argument");
+    int rc;
+    if ((rc = check_level_arg(level)) || (rc = check_board_count(n))) return rc;
+    if (n == 0) return SDK_OK;
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCALL(hipSetDevice(c->device));
+    return launch_reduce_level(c, static_cast<const uint8_t*>(d_in), static_cast<const uint8_t*>(d_order), level,
+                               static_cast<uint8_t*>(d_out), static_cast<int8_t*>(d_status), n);
+}
+
+int sdk_minimize_level_batch(sdk_ctx* c, const uint8_t* in, const uint8_t* order, int level, uint8_t* out,
+                             int8_t* status, size_t n) {
+    if (!c || (n && (!in || !order || !out || !status))) return fail(SDK_EINVAL, "NULL argument");
+    int rc;
+    if ((rc = check_level_arg(level)) || (rc = check_board_count(n))) return rc;
+    if (n == 0) return SDK_OK;
+    if ((rc = check_order_rows(order, n))) return rc;
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCALL(hipSetDevice(c->device));
+    if ((rc = ensure(c->in, n * 81)) || (rc = ensure(c->mz_order, n * 81)) || (rc = ensure(c->out, n * 81)) ||
+        (rc = ensure(c->status, n)))
+        return rc;
+    uint8_t* d_in = static_cast<uint8_t*>(c->in.p);
+    uint8_t* d_order = static_cast<uint8_t*>(c->mz_order.p);
+    uint8_t* d_out = static_cast<uint8_t*>(c->out.p);
+    int8_t* d_status = static_cast<int8_t*>(c->status.p);
+    Staging io(c, {{n * 81, order, d_order}, {n * 81, in, d_in, d_out, out}, {n, nullptr, nullptr, d_status, status}});
+    if ((rc = io.send()) || (rc = launch_reduce_level(c, d_in, d_order, level, d_out, d_status, n))) return rc;
+    return io.fetch();
+}
+
+int sdk_generate_level_dev(sdk_ctx* c, uint64_t seed, uint64_t first, size_t n, int level, void* d_puzzles,
+                           void* d_grids, void* d_status) {
+    if (!c || (n && (!d_puzzles || !d_grids || !d_status))) return fail(SDK_EINVAL, "NULL argument");
+    int rc;
+    if ((rc = check_level_arg(level)) || (rc = check_generate_args(first, n))) return rc;
+    if (n == 0) return SDK_OK;
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCALL(hipSetDevice(c->device));
+    return launch_generate_level(c, seed, first, n, level, static_cast<uint8_t*>(d_puzzles),
+                                 static_cast<uint8_t*>(d_grids), static_cast<int8_t*>(d_status));
+}
+
+int sdk_generate_level(sdk_ctx* c, uint64_t seed, uint64_t first, size_t n, int level, uint8_t* puzzles,
+                       uint8_t* grids, int8_t* status) {
+    if (!c || (n && (!puzzles || !grids || !status))) return fail(SDK_EINVAL, "NULL argument");
+    int rc;
+    if ((rc = check_level_arg(level)) || (rc = check_generate_args(first, n))) return rc;
+    if (n == 0) return SDK_OK;
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCALL(hipSetDevice(c->device));
+    if ((rc = ensure(c->in, n * 81)) || (rc = ensure(c->out, n * 81)) || (rc = ensure(c->status, n))) return rc;
+    uint8_t* d_grids = static_cast<uint8_t*>(c->in.p);
+    uint8_t* d_puzzles = static_cast<uint8_t*>(c->out.p);
+    int8_t* d_status = static_cast<int8_t*>(c->status.p);
+    Staging io(c, {{n * 81, nullptr, nullptr, d_puzzles, puzzles},
+                   {n * 81, nullptr, nullptr, d_grids, grids},
+                   {n, nullptr, nullptr, d_status, status}});
+    if ((rc = launch_generate_level(c, seed, first, n, level, d_puzzles, d_grids, d_status))) return rc;
     return io.fetch();
 }
 

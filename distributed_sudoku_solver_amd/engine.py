@@ -394,6 +394,50 @@ class SudokuEngine:
         return out, status
 
     @staticmethod
+    def _check_level(level):
+        level = int(level)
+        if not L.SDK_GRADE_NAKED <= level <= L.SDK_GRADE_LOCKED:
+            raise ValueError("level must be 1 (naked singles), 2 (+ hidden singles) or 3 (+ locked candidates)")
+        return level
+
+    def minimize_level_batch(self, boards, level, order=None, seed=0):
+        """uint8[n,81] -> (puzzles uint8[n,81], status int8[n]): clue removal that stops at a technique
+        level, on the GPU (sdk_minimize_level_batch).  status[i] is 1 when board i has clean givens and
+        the techniques of `level` (grade_batch's levels 1..3) close it; every other board comes back
+        unchanged with status 0.  An eligible board loses, in the cell order of order[i] (as in
+        minimize_batch, and drawn from `seed` the same way when None), every clue without which those
+        techniques still close it: grade_batch gives the result a level <= `level`, and no clue of it
+        can go at that level.  A bad level or order raises ValueError before any launch.  Like
+        grade_batch this call is not sharded by MultiDeviceEngine or ShardedBatch."""
+        level = self._check_level(level)
+        boards = np.ascontiguousarray(boards, dtype=np.uint8).reshape(-1, 81)
+        n = boards.shape[0]
+        if order is None:
+            order = np.random.default_rng(seed).permuted(np.tile(np.arange(81, dtype=np.uint8), (n, 1)), axis=1)
+        order = self.check_order(order, n)
+        out = np.empty_like(boards)
+        status = np.empty(n, dtype=np.int8)
+        L.check(self.lib.sdk_minimize_level_batch(self.ctx, _ptr(boards), _ptr(order), level, _ptr(out), _ptr(status),
+                                                  n),
+                "sdk_minimize_level_batch")
+        return out, status
+
+    def generate_level(self, n, level, seed=synth.DEFAULT_SEED + 3, lo=0):
+        """Rows [lo, lo+n) of the stream of puzzles minimal for a technique level, made on the GPU
+        (sdk_generate_level: generate_grids, then minimize_level_batch in the grids' own removal
+        orders): (puzzles uint8[n,81], solutions uint8[n,81], status int8[n]).  Row k depends only on
+        (seed, k, level); status is 1 for every row (a grid dropped by SDK_OPT_GEN_CAP is 0, zeros in
+        both)."""
+        level = self._check_level(level)
+        n, seed, lo = self._stream_rows(n, seed, lo)
+        puzzles = np.empty((n, 81), dtype=np.uint8)
+        grids = np.empty((n, 81), dtype=np.uint8)
+        status = np.empty(n, dtype=np.int8)
+        L.check(self.lib.sdk_generate_level(self.ctx, seed, lo, n, level, _ptr(puzzles), _ptr(grids), _ptr(status)),
+                "sdk_generate_level")
+        return puzzles, grids, status
+
+    @staticmethod
     def _stream_rows(n, seed, lo):
         n, seed, lo = int(n), int(seed), int(lo)
         if n < 0 or not 0 <= seed < (1 << 64) or not 0 <= lo < (1 << 64):
@@ -740,6 +784,18 @@ class SudokuEngine:
         """The order rows are not validated on this path (see include/sudoku_hip.h)."""
         L.check(self.lib.sdk_minimize_batch_dev(self.ctx, d_in.ptr, d_order.ptr, d_out.ptr, d_status.ptr, int(n)),
                 "sdk_minimize_batch_dev")
+
+    def minimize_level_batch_dev(self, d_in, d_order, level, d_out, d_status, n):
+        """The level and the order rows are not validated on this path (see include/sudoku_hip.h);
+        d_out may be d_in."""
+        L.check(self.lib.sdk_minimize_level_batch_dev(self.ctx, d_in.ptr, d_order.ptr, int(level), d_out.ptr,
+                                                      d_status.ptr, int(n)),
+                "sdk_minimize_level_batch_dev")
+
+    def generate_level_dev(self, d_puzzles, d_grids, d_status, n, level, seed=synth.DEFAULT_SEED + 3, lo=0):
+        L.check(self.lib.sdk_generate_level_dev(self.ctx, int(seed), int(lo), int(n), int(level), d_puzzles.ptr,
+                                                d_grids.ptr, d_status.ptr),
+                "sdk_generate_level_dev")
 
     def generate_grids_dev(self, d_grids, n, seed=synth.DEFAULT_SEED + 3, lo=0, d_order=None, d_placements=None):
         L.check(self.lib.sdk_generate_grids_dev(self.ctx, int(seed), int(lo), int(n), d_grids.ptr,

@@ -18,7 +18,7 @@
  *   and inside the search level the number of single-cell backdoors)
  *       -> sdk_classify_batch, sdk_grade_batch, sdk_rate_batch, sdk_subsets_batch
  *       -> sdk_generate_puzzles, sdk_generate_graded, sdk_generate_rated,
- *          sdk_generate_subsets
+ *          sdk_generate_subsets, sdk_minimize_level_batch, sdk_generate_level
  *   DFS subtree split across ring nodes (NEEDWORK/TASK, DHT_Node.py:491-510,
  *   225-250; utils.py:1-9) -- within one node of GPUs:
  *       -> sdk_frontier_* + sdk_comm_* (RCCL over xGMI)
@@ -53,6 +53,7 @@ extern "C" {
                             /* and sdk_grade_batch[_dev] and sdk_generate_graded[_dev]            */
                             /* and sdk_rate_batch[_dev] and sdk_generate_rated[_dev]              */
                             /* and sdk_subsets_batch[_dev] and sdk_generate_subsets[_dev]         */
+                            /* and sdk_minimize_level_batch[_dev], sdk_generate_level[_dev]       */
                             /* (new symbols only: nothing a version-2 caller uses changed)        */
 
 /* return codes */
@@ -376,6 +377,36 @@ int sdk_generate_grids(sdk_ctx *ctx, uint64_t seed, uint64_t first, size_t n, ui
 int sdk_generate_puzzles(sdk_ctx *ctx, uint64_t seed, uint64_t first, size_t n, uint8_t *puzzles,
                          uint8_t *grids, int8_t *status);
 
+/* Clue removal that stops at a technique level.  R_level is sdk_grade_batch's technique set of that
+ * level (naked singles; + hidden singles; + locked candidates) and "R_level closes a board" means its
+ * fixpoint F_level has every cell closed -- such a board has exactly one completion, so no search is
+ * involved.  level must be SDK_GRADE_NAKED..SDK_GRADE_LOCKED, else SDK_EINVAL.  order as for
+ * sdk_minimize_batch (rows that are not permutations of 0..80: SDK_EINVAL).  Per board:
+ *   board i is eligible when its givens are clean (each 1..9, none twice in a unit) and R_level
+ *   closes it: status[i] = 1.  Every other board -- inert or duplicated givens, no or several
+ *   completions, one that needs more than R_level -- has status[i] = 0 and out[i] = the input, byte
+ *   for byte;
+ *   for an eligible board and q = 0..80 the cell order[i][q], if non-zero, is cleared, and put back
+ *   unless R_level still closes the board without it.
+ * out[i] is the result: a pure function of (board, order row, level); sdk_grade_batch gives it a
+ * level <= `level`, and none of its clues can go under R_level (removing a given only enlarges every
+ * candidate set, so a removal that failed in its round fails at every later state: one pass over
+ * the order is enough).  One launch per slice: a group of 64 boards runs its eligibility test and
+ * its 81 rounds inside reduce32_kernel.h.  out may be in.  Any n up to 2^31-1 (slices of 2^24
+ * boards); one span under SDK_OPT_TIMING; no option is changed. */
+int sdk_minimize_level_batch(sdk_ctx *ctx, const uint8_t *in, const uint8_t *order, int level,
+                             uint8_t *out, int8_t *status, size_t n);
+
+/* Level-minimal puzzles, made on the GPU: the grids of sdk_generate_grids, then
+ * sdk_minimize_level_batch over them in their own removal orders (kept in a context buffer), all
+ * enqueued without the host.  Row i is a pure function of (seed, first + i, level).
+ *   puzzles  uint8[n][81];  grids  uint8[n][81], the puzzles' completions;
+ *   status   the minimiser's: 1 for every grid that was kept.  A grid that was not (see
+ *            SDK_OPT_GEN_CAP) is 81 zeros: status 0, and its puzzle row is 81 zeros too.
+ * All three are required; level as above.  One span under SDK_OPT_TIMING. */
+int sdk_generate_level(sdk_ctx *ctx, uint64_t seed, uint64_t first, size_t n, int level,
+                       uint8_t *puzzles, uint8_t *grids, int8_t *status);
+
 /* Puzzles of a requested grade: the first n puzzles of the stream, from index `first` on, that match
  * a predicate -- generated, graded and selected on the GPU; only the matches leave the device.
  *
@@ -620,6 +651,14 @@ int sdk_generate_grids_dev(sdk_ctx *ctx, uint64_t seed, uint64_t first, size_t n
                            void *d_order, void *d_placements);
 int sdk_generate_puzzles_dev(sdk_ctx *ctx, uint64_t seed, uint64_t first, size_t n, void *d_puzzles,
                              void *d_grids, void *d_status);
+/* d_in and d_out 16-byte aligned (else SDK_EINVAL; d_out may be d_in).  The order rows are not
+ * validated here: an entry >= 81 is "no cell" (that round leaves the board unchanged), and a
+ * repeated cell is tried again (a no-op: it is empty, or it could not go). */
+int sdk_minimize_level_batch_dev(sdk_ctx *ctx, const void *d_in, const void *d_order, int level,
+                                 void *d_out, void *d_status, size_t n);
+/* d_puzzles and d_grids 16-byte aligned, else SDK_EINVAL */
+int sdk_generate_level_dev(sdk_ctx *ctx, uint64_t seed, uint64_t first, size_t n, int level,
+                           void *d_puzzles, void *d_grids, void *d_status);
 /* d_puzzles and d_grids 16-byte aligned (and d_index 8-byte), else SDK_EINVAL; d_level, d_open,
  * d_index and scanned nullable; found and scanned are host pointers.  The call returns when the scan
  * is decided (it waits for every round's count): *found and *scanned are final then, and the device
