@@ -109,6 +109,18 @@ SDK_COMM_RECV = 1
 # every symbol the header declares: name -> (restype, argtypes)
 _vp = ctypes.c_void_p
 _sz = ctypes.c_size_t
+
+
+class SelectRows(ctypes.Structure):
+    """sdk_select_rows (include/sudoku_hip.h): the arguments of sdk_select_rows_dev, field for field."""
+    _fields_ = ([(k, _vp) for k in ("puzzles", "grids", "status", "level", "open", "backdoors", "key", "open4")]
+                + [(k, ctypes.c_uint64) for k in ("m", "first", "base", "n")]
+                + [(k, ctypes.c_uint32) for k in ("level_mask", "clues_lo", "clues_hi", "backdoors_lo",
+                                                  "backdoors_hi", "open4_lo", "open4_hi")]
+                + [(k, _vp) for k in ("out_puzzles", "out_grids", "out_level", "out_open", "out_index",
+                                      "out_backdoors", "out_key", "out_open4")])
+
+
 SIGNATURES = {
     "sdk_abi_version": (ctypes.c_int, []),
     "sdk_last_error": (ctypes.c_char_p, []),
@@ -165,6 +177,8 @@ SIGNATURES = {
                                                 ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
                                                 ctypes.c_uint64, ctypes.c_uint64, _vp, _vp, _vp, _vp, _vp, _vp,
                                                 ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]),
+    "sdk_select_rows_dev": (ctypes.c_int, [_vp, ctypes.POINTER(SelectRows), ctypes.POINTER(ctypes.c_uint64),
+                                           ctypes.POINTER(ctypes.c_uint64)]),
     "sdk_frontier_boards_dev": (ctypes.c_int, [_vp, ctypes.POINTER(_vp), ctypes.POINTER(ctypes.c_uint64)]),
     "sdk_frontier_load_dev": (ctypes.c_int, [_vp, _vp, ctypes.c_uint64]),
     "sdk_frontier_refine_range": (ctypes.c_int, [_vp, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64,

@@ -1367,6 +1367,80 @@ struct GradedCall {
     uint8_t* open4 = nullptr;
 };
 
+// One round's selection (select_kernel.h): rows [0, m) of caller-supplied buffers -- a round of
+// launch_generate_graded, or the rows of sdk_select_rows_dev -- ranked behind the d_word->total hits of
+// the earlier rounds.  This is the only place that fills the three argument structs and makes the
+// three launches; it enqueues, and neither allocates, reads back nor synchronizes: the caller sizes the
+// per-tile buffers (ballot, popcount, offset) before its first launch and its timing span -- a grow is a
+// hipFree, which waits for the device -- and reads the word.  puzzles and grids hold whole tiles.
+struct SelectRound {
+    const uint8_t *puzzles, *grids;
+    const int8_t* status;
+    const uint8_t *level, *open;
+    const uint8_t *backdoors, *key, *open4;     // nullable
+    uint32_t m;
+    uint64_t first;                             // stream index of row 0
+    uint32_t n;                                 // the quota
+    uint32_t level_mask, clues_lo, clues_hi, bd_lo, bd_hi, o4_lo, o4_hi;
+    uint8_t *out_puzzles, *out_grids;
+    uint8_t *out_level, *out_open;              // nullable, as the rest
+    uint64_t* out_index;
+    uint8_t *out_backdoors, *out_key, *out_open4;
+};
+
+int launch_select_round(sdk_ctx* c, const SelectRound& r, sdk::SelWord* d_word) {
+    const uint32_t tiles = (r.m + sdk::kSelTileRows - 1) / sdk::kSelTileRows;
+    if (c->gg_ballot.bytes < (size_t)tiles * 8 || c->gg_count.bytes < (size_t)tiles * 4 ||
+        c->gg_offset.bytes < (size_t)tiles * 4)
+        return fail(SDK_EINVAL, "selection buffers not sized before the round");
+    sdk::SelFlagArgs fa{};
+    fa.puzzles = r.puzzles;
+    fa.status = r.status;
+    fa.level = r.level;
+    fa.m = r.m;
+    fa.level_mask = r.level_mask;
+    fa.clues_lo = r.clues_lo;
+    fa.clues_hi = r.clues_hi;
+    fa.backdoors = r.backdoors;
+    fa.bd_lo = r.bd_lo;
+    fa.bd_hi = r.bd_hi;
+    fa.open4 = r.open4;
+    fa.o4_lo = r.o4_lo;
+    fa.o4_hi = r.o4_hi;
+    fa.ballot = static_cast<unsigned long long*>(c->gg_ballot.p);
+    fa.count = static_cast<uint32_t*>(c->gg_count.p);
+    sdk::SelScanArgs sa{};
+    sa.count = fa.count;
+    sa.offset = static_cast<uint32_t*>(c->gg_offset.p);
+    sa.tiles = tiles;
+    sa.word = d_word;
+    sdk::SelScatterArgs ca{};
+    ca.puzzles = r.puzzles;
+    ca.grids = r.grids;
+    ca.level = r.level;
+    ca.open = r.open;
+    ca.ballot = fa.ballot;
+    ca.offset = sa.offset;
+    ca.first = r.first;
+    ca.n = r.n;
+    ca.out_puzzles = r.out_puzzles;
+    ca.out_grids = r.out_grids;
+    ca.out_level = r.out_level;
+    ca.out_open = r.out_open;
+    ca.out_index = r.out_index;
+    ca.backdoors = r.backdoors;
+    ca.key = r.key;
+    ca.out_backdoors = r.out_backdoors;
+    ca.out_key = r.out_key;
+    ca.open4 = r.open4;
+    ca.out_open4 = r.out_open4;
+    ca.word = d_word;
+    HIPCALL(sdk::launch_select_flag(fa, tiles, c->stream));
+    HIPCALL(sdk::launch_select_scan(sa, c->stream));
+    HIPCALL(sdk::launch_select_scatter(ca, tiles, c->stream));
+    return SDK_OK;
+}
+
 int launch_generate_graded(sdk_ctx* c, const GradedCall& g, uint64_t* found, uint64_t* scanned) {
     if ((reinterpret_cast<uintptr_t>(g.puzzles) | reinterpret_cast<uintptr_t>(g.grids)) & 15u)
         return fail(SDK_EINVAL, "device boards must be 16-byte aligned");
@@ -1402,6 +1476,7 @@ int launch_generate_graded(sdk_ctx* c, const GradedCall& g, uint64_t* found, uin
         if ((rc = ensure(c->gg_puz, rows * 81)) || (rc = ensure(c->gg_grid, rows * 81)) ||
             (rc = ensure(c->gg_sol, rows * 81)) || (rc = ensure(c->gg_st, rows)) || (rc = ensure(c->gg_gst, rows)) ||
             (rc = ensure(c->gg_level, rows)) || (rc = ensure(c->gg_open, rows)) ||
+            // (launch_select_round's per-tile buffers)
             (rc = ensure(c->gg_ballot, (size_t)tiles * 8)) || (rc = ensure(c->gg_count, (size_t)tiles * 4)) ||
             (rc = ensure(c->gg_offset, (size_t)tiles * 4)))
             return rc;
@@ -1421,51 +1496,34 @@ int launch_generate_graded(sdk_ctx* c, const GradedCall& g, uint64_t* found, uin
             (rc = launch_grade(c, puz, static_cast<uint8_t*>(c->gg_sol.p), static_cast<int8_t*>(c->gg_gst.p), level,
                                open, m, 0, bd, key, o4)))
             return rc;
-        sdk::SelFlagArgs fa{};
-        fa.puzzles = puz;
-        fa.status = st;
-        fa.level = level;
-        fa.m = (uint32_t)m;
-        fa.level_mask = g.level_mask;
-        fa.clues_lo = g.clues_lo;
-        fa.clues_hi = g.clues_hi;
-        fa.backdoors = bd;
-        fa.bd_lo = g.bd_lo;
-        fa.bd_hi = g.bd_hi;
-        fa.open4 = o4;
-        fa.o4_lo = g.o4_lo;
-        fa.o4_hi = g.o4_hi;
-        fa.ballot = static_cast<unsigned long long*>(c->gg_ballot.p);
-        fa.count = static_cast<uint32_t*>(c->gg_count.p);
-        sdk::SelScanArgs sa{};
-        sa.count = fa.count;
-        sa.offset = static_cast<uint32_t*>(c->gg_offset.p);
-        sa.tiles = tiles;
-        sa.word = d_word;
-        sdk::SelScatterArgs ca{};
-        ca.puzzles = puz;
-        ca.grids = grid;
-        ca.level = level;
-        ca.open = open;
-        ca.ballot = fa.ballot;
-        ca.offset = sa.offset;
-        ca.first = g.first + done;
-        ca.n = g.n;
-        ca.out_puzzles = g.puzzles;
-        ca.out_grids = g.grids;
-        ca.out_level = g.level;
-        ca.out_open = g.open;
-        ca.out_index = g.index;
-        ca.backdoors = bd;
-        ca.key = key;
-        ca.out_backdoors = g.backdoors;
-        ca.out_key = g.key;
-        ca.open4 = o4;
-        ca.out_open4 = g.open4;
-        ca.word = d_word;
-        HIPCALL(sdk::launch_select_flag(fa, tiles, c->stream));
-        HIPCALL(sdk::launch_select_scan(sa, c->stream));
-        HIPCALL(sdk::launch_select_scatter(ca, tiles, c->stream));
+        SelectRound r{};
+        r.puzzles = puz;
+        r.grids = grid;
+        r.status = st;
+        r.level = level;
+        r.open = open;
+        r.backdoors = bd;
+        r.key = key;
+        r.open4 = o4;
+        r.m = (uint32_t)m;
+        r.first = g.first + done;
+        r.n = g.n;
+        r.level_mask = g.level_mask;
+        r.clues_lo = g.clues_lo;
+        r.clues_hi = g.clues_hi;
+        r.bd_lo = g.bd_lo;
+        r.bd_hi = g.bd_hi;
+        r.o4_lo = g.o4_lo;
+        r.o4_hi = g.o4_hi;
+        r.out_puzzles = g.puzzles;
+        r.out_grids = g.grids;
+        r.out_level = g.level;
+        r.out_open = g.open;
+        r.out_index = g.index;
+        r.out_backdoors = g.backdoors;
+        r.out_key = g.key;
+        r.out_open4 = g.open4;
+        if ((rc = launch_select_round(c, r, d_word))) return rc;
         sdk::SelWord word;
         HIPCALL(hipMemcpyAsync(&word, d_word, sizeof word, hipMemcpyDeviceToHost, c->stream));
         HIPCALL(hipStreamSynchronize(c->stream));
@@ -2818,6 +2876,75 @@ int sdk_generate_subsets(sdk_ctx* c, uint64_t seed, uint64_t first, size_t n, ui
     *found = f;
     if (scanned) *scanned = s;
     return SDK_OK;
+}
+
+int sdk_select_rows_dev(sdk_ctx* c, const sdk_select_rows* a, uint64_t* total, uint64_t* last) {
+    if (!c || !a || !total || !last) return fail(SDK_EINVAL, "NULL argument");
+    if (!a->puzzles || !a->grids || !a->status || !a->level || !a->open || !a->out_puzzles || !a->out_grids)
+        return fail(SDK_EINVAL, "NULL argument: the rows, status, level, open and both board outputs are required");
+    if (a->m == 0 || a->m > kGradedChunkMax) return fail(SDK_EINVAL, "m must be 1..2^24");
+    if (a->first > UINT64_MAX - a->m) return fail(SDK_EINVAL, "first + m overflows the stream index");
+    int rc;
+    if (a->n == 0) return fail(SDK_EINVAL, "n must be at least 1");
+    if (a->n > 0x7FFFFFFFull) return fail(SDK_EINVAL, "n must be at most 2^31-1 rows");
+    if (a->base >= a->n) return fail(SDK_EINVAL, "base must be below n (a round starts only below the quota)");
+    if ((rc = check_graded_args(a->first, (size_t)a->n, a->level_mask, a->clues_lo, a->clues_hi, a->m, 0)) ||
+        (rc = check_rated_range(a->backdoors_lo, a->backdoors_hi)) ||
+        (rc = check_subsets_range(a->open4_lo, a->open4_hi)))
+        return rc;
+    if ((reinterpret_cast<uintptr_t>(a->puzzles) | reinterpret_cast<uintptr_t>(a->grids)) & 15u)
+        return fail(SDK_EINVAL, "the rows must be 16-byte aligned");
+    if ((reinterpret_cast<uintptr_t>(a->out_puzzles) | reinterpret_cast<uintptr_t>(a->out_grids)) & 15u)
+        return fail(SDK_EINVAL, "device boards must be 16-byte aligned");
+    if (reinterpret_cast<uintptr_t>(a->out_index) & 7u) return fail(SDK_EINVAL, "out_index must be 8-byte aligned");
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCALL(hipSetDevice(c->device));
+    const uint32_t tiles = (uint32_t)((a->m + sdk::kSelTileRows - 1) / sdk::kSelTileRows);
+    if ((rc = ensure(c->gg_word, sizeof(sdk::SelWord))) || (rc = ensure(c->gg_ballot, (size_t)tiles * 8)) ||
+        (rc = ensure(c->gg_count, (size_t)tiles * 4)) || (rc = ensure(c->gg_offset, (size_t)tiles * 4)))
+        return rc;
+    sdk::SelWord* d_word = static_cast<sdk::SelWord*>(c->gg_word.p);
+    SelectRound r{};
+    r.puzzles = static_cast<const uint8_t*>(a->puzzles);
+    r.grids = static_cast<const uint8_t*>(a->grids);
+    r.status = static_cast<const int8_t*>(a->status);
+    r.level = static_cast<const uint8_t*>(a->level);
+    r.open = static_cast<const uint8_t*>(a->open);
+    r.backdoors = static_cast<const uint8_t*>(a->backdoors);
+    r.key = static_cast<const uint8_t*>(a->key);
+    r.open4 = static_cast<const uint8_t*>(a->open4);
+    r.m = (uint32_t)a->m;
+    r.first = a->first;
+    r.n = (uint32_t)a->n;
+    r.level_mask = a->level_mask;
+    r.clues_lo = a->clues_lo;
+    r.clues_hi = a->clues_hi;
+    r.bd_lo = a->backdoors_lo;
+    r.bd_hi = a->backdoors_hi;
+    r.o4_lo = a->open4_lo;
+    r.o4_hi = a->open4_hi;
+    r.out_puzzles = static_cast<uint8_t*>(a->out_puzzles);
+    r.out_grids = static_cast<uint8_t*>(a->out_grids);
+    r.out_level = static_cast<uint8_t*>(a->out_level);
+    r.out_open = static_cast<uint8_t*>(a->out_open);
+    r.out_index = static_cast<uint64_t*>(a->out_index);
+    r.out_backdoors = static_cast<uint8_t*>(a->out_backdoors);
+    r.out_key = static_cast<uint8_t*>(a->out_key);
+    r.out_open4 = static_cast<uint8_t*>(a->out_open4);
+    TimedSpan span(c);
+    if ((rc = span.begin())) return rc;
+    // the word: {base, 0}
+    HIPCALL(hipMemsetAsync(d_word, 0, sizeof(sdk::SelWord), c->stream));
+    if (a->base) HIPCALL(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(&d_word->total), (int)(uint32_t)a->base, 1, c->stream));
+    if ((rc = launch_select_round(c, r, d_word))) return rc;
+    sdk::SelWord word;
+    HIPCALL(hipMemcpyAsync(&word, d_word, sizeof word, hipMemcpyDeviceToHost, c->stream));
+    HIPCALL(hipStreamSynchronize(c->stream));
+    if (word.total >= r.n && (word.last == 0 || word.last > r.m))
+        return fail(SDK_EHIP, "selection lost the position of its last hit");
+    *total = word.total;
+    *last = word.last;
+    return span.end(SDK_OK);
 }
 
 int sdk_count_solutions(sdk_ctx* c, const uint8_t* board, uint64_t limit, uint64_t* count, int8_t* status) {

@@ -849,3 +849,12 @@ class SudokuEngine:
                                                   ctypes.byref(scanned)),
                 "sdk_generate_subsets_dev")
         return found.value, scanned.value
+
+    def select_rows_dev(self, rows):
+        """One round of the graded selection on caller-supplied device rows (sdk_select_rows_dev): `rows`
+        is an L.SelectRows of device addresses and scalars -> (total, last).  puzzles and grids hold
+        whole tiles of 64 rows; the outputs are valid on return."""
+        total, last = ctypes.c_uint64(), ctypes.c_uint64()
+        L.check(self.lib.sdk_select_rows_dev(self.ctx, ctypes.byref(rows), ctypes.byref(total), ctypes.byref(last)),
+                "sdk_select_rows_dev")
+        return total.value, last.value

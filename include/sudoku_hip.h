@@ -54,6 +54,7 @@ extern "C" {
                             /* and sdk_rate_batch[_dev] and sdk_generate_rated[_dev]              */
                             /* and sdk_subsets_batch[_dev] and sdk_generate_subsets[_dev]         */
                             /* and sdk_minimize_level_batch[_dev], sdk_generate_level[_dev]       */
+                            /* and sdk_select_rows_dev                                            */
                             /* (new symbols only: nothing a version-2 caller uses changed)        */
 
 /* return codes */
@@ -684,6 +685,41 @@ int sdk_generate_subsets_dev(sdk_ctx *ctx, uint64_t seed, uint64_t first, size_t
                              void *d_puzzles, void *d_grids, void *d_level, void *d_open,
                              void *d_open4,
                              void *d_index, uint64_t *found, uint64_t *scanned);
+
+/* One round of the selection behind sdk_generate_graded / _rated / _subsets (select_kernel.h), on rows
+ * the caller supplies instead of rows the generator and the grader made: the seam through which the
+ * selection kernels are tested.  Row i (0 <= i < m) is a hit when status[i] == SDK_SOLVED, level[i] < 32
+ * and bit level[i] of level_mask is set, clues_lo <= (non-zero bytes of puzzles[i]) <= clues_hi, and,
+ * if level[i] == SDK_GRADE_SEARCH, backdoors_lo <= backdoors[i] <= backdoors_hi where `backdoors` is
+ * given and open4_lo <= open4[i] <= open4_hi where `open4` is given.  The hits keep their order and
+ * take the ranks base, base + 1, ...; a hit of rank r < n is written to row r of every output that is
+ * given: its puzzle and grid row, level, open, first + i, and backdoors / key / open4 (SDK_RATE_NONE /
+ * SDK_SUBSETS_NONE, 0xFF, where that source is NULL).  Nothing else of an output is written.
+ *   puzzles, grids  uint8[tiles * 64][81] with tiles = ceil(m / 64): WHOLE tiles of 64 rows, 16-byte
+ *                   aligned.  The rows from m to the end of the last tile are read and ignored; the
+ *                   call cannot check that they are there.
+ *   status  int8[m];  level, open  uint8[m];  backdoors, key, open4  uint8[m] or NULL;
+ *   m       1..2^24;  first + m must not overflow;
+ *   n       the quota, 1..2^31-1;  base < n: the hits of the earlier rounds;
+ *   level_mask and the three ranges: as sdk_generate_graded, _rated and _subsets;
+ *   out_puzzles, out_grids  uint8[n][81], 16-byte aligned, required;  out_level, out_open,
+ *                   out_backdoors, out_key, out_open4  uint8[n] or NULL;  out_index  uint64[n] or NULL.
+ * All of these are device pointers.  *total = base + every hit of the rows, whatever the quota;
+ * *last = 1 + the row of the hit of rank n - 1, or 0 when that hit is not among these rows (host
+ * pointers, both required).  Rounds chain: a stream cut into calls with base = the call before's
+ * *total writes what one call over the whole stream writes.  The call sets the context's selection
+ * word to {base, 0}, enqueues the three launches, reads the word back (8 bytes) and returns; it is one
+ * span under SDK_OPT_TIMING.  A bad argument is SDK_EINVAL: nothing is launched or written. */
+typedef struct sdk_select_rows {
+    const void *puzzles, *grids, *status, *level, *open;
+    const void *backdoors, *key, *open4;
+    uint64_t m, first, base, n;
+    uint32_t level_mask, clues_lo, clues_hi;
+    uint32_t backdoors_lo, backdoors_hi, open4_lo, open4_hi;
+    void *out_puzzles, *out_grids, *out_level, *out_open, *out_index;
+    void *out_backdoors, *out_key, *out_open4;
+} sdk_select_rows;
+int sdk_select_rows_dev(sdk_ctx *ctx, const sdk_select_rows *rows, uint64_t *total, uint64_t *last);
 
 /* Kernel time accounting (HIP events on the context stream, bracketing every
  * kernel launched by the *_dev / host calls since the last reset).  Only with
