@@ -24,6 +24,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "check_args.h"
+
 // Round 6 (checker): the fast path is entered on one OR over the record (every byte < 32)
 // and left for the exact path on the OR of the one-hot terms (a byte in 10..31), and the verdicts
 // are non-temporal stores: 1.364 ms per 100M boards against 1.392 on one box (0 to fall back)
@@ -38,7 +40,6 @@ namespace sdk {
 
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
-constexpr int kCheckThreads = 256;
 constexpr int kCheckTileBytes = kCheckThreads * 81;          // 20736
 constexpr int kCheckTileVec = kCheckTileBytes / 16;          // 1296 x uint4
 
@@ -403,7 +404,7 @@ __device__ __forceinline__ bool unit_ok_i64(const int64_t (&u)[9]) {
     return sum == 45 && distinct;
 }
 
-__global__ __launch_bounds__(256) void check_kernel_i64(const int64_t* __restrict__ boards, uint8_t* __restrict__ out,
+__global__ __launch_bounds__(kCheckI64Threads) void check_kernel_i64(const int64_t* __restrict__ boards, uint8_t* __restrict__ out,
                                                         uint64_t n) {
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
         const int64_t* b = boards + i * 81;

@@ -1,5 +1,6 @@
 // donate_args.h -- the layout of a subtree-donation area (solve4_kernel.h, "subtree donation", has the protocol)
-// and of the split phase's saved stacks.  The host sizes, zeroes and reads these areas (sudoku_hip.hip); plain C++.
+// and of the split phase's saved stacks.  The host sizes, zeroes and reads these areas
+// (sudoku_hip.hip); the list kernels that feed a donation launch are donate_launch.hip's.  Plain C++.
 #pragma once
 #include <hip/hip_vector_types.h>
 
@@ -17,7 +18,7 @@ struct DnXcd {
 };
 // Resumed split boards (round 4).  The split phase leaves the stack of a board that reaches
 // the split budget (split_save4); the collect kernel reserves records and items for it, and
-// dn_seed_kernel (sudoku_hip.hip) turns its open subtrees -- the current node's and every
+// dn_seed_kernel (donate_launch.hip) turns its open subtrees -- the current node's and every
 // level's untried digits -- into items of a board record before the donation launch.  Idle
 // waves take those items from the seed queue first (dn_idle4), so the heavy boards go on
 // from where the split phase left them, spread over the grid, instead of restarting.
@@ -117,6 +118,32 @@ struct SplitSave {
     uint32_t pad[31];
     uint2 hdr[kSaveCap];      // (board, depth)
     uint2 lv[kSaveCap][kSaveLv][32];
+};
+
+// What dn_collect_kernel needs to resume split boards (`save` null: every listed board restarts): the
+// split phase's saved stacks and each board's entry, the donation area whose DnSeed takes the
+// reservations, and the seed list.
+struct DnResume {
+    const SplitSave* save;
+    const uint32_t* save_idx;
+    DnCtl* ctl;
+    uint32_t* seeds;          // [0] seeded boards, [1] restarted boards, then (board, entry) pairs
+};
+// A phased solve's control words, zeroed in one launch before its first phase: the split
+// phase's dequeue counter and heads, the statistics, both donation launches' control blocks
+// (their epochs set) and list lengths.
+struct DnPrep {
+    uint32_t* counter;
+    uint32_t* heads;
+    uint32_t heads_words;
+    uint32_t* stat;
+    uint32_t* ctl[2];
+    uint32_t epoch[2];
+    uint32_t fault;      // DnCtl.fault (SDK_OPT_DN_FAULT, test only)
+    uint32_t helpers;    // DnCtl.helpers (SDK_OPT_DONATE_HELPERS)
+    uint32_t* list[2];
+    uint32_t* seeds;     // the seed list's two length words (nullable)
+    uint32_t* save;      // SplitSave::count (nullable)
 };
 
 }  // namespace sdk

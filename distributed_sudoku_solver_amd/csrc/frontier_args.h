@@ -1,5 +1,5 @@
 // frontier_args.h -- the frontier build's control block and expansion arguments, shared by
-// frontier_kernel.h (sudoku_hip.hip) and expand4_kernel.h (solve4_launch.hip).
+// frontier_kernel.h (frontier_launch.hip), expand4_kernel.h (solve4_launch.hip) and the host (sudoku_hip.hip).
 #pragma once
 #include <cstdint>
 

@@ -40,13 +40,12 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "generate_args.h"
+
 namespace sdk {
 
-constexpr int kGenThreads = 64;             // one wave per workgroup (waves share nothing)
-constexpr int kGenWavesPerCu = 6;           // what the LDS holds
 constexpr int kGenSteps = 32;               // steps between refills
 constexpr uint32_t kGenAll = 0x3FEu;        // digits 1..9 as bits 1..9 (gen_minimal.c's layout)
-constexpr uint32_t kGenFloor = 1u << 20;    // the fill's own bound is never below this (= the default cap)
 
 struct GenLds {
     uint32_t stk[81][64];                   // untried digits of each level; after the fill, the order bytes
@@ -54,18 +53,6 @@ struct GenLds {
     uint8_t dig[41][64];                    // digit placed in cell c: nibble c & 1 of byte c >> 1
 };
 static_assert(sizeof(GenLds) == 26816, "six waves per CU");
-
-struct GenArgs {
-    uint64_t seed_mul;       // seed * 0x100000001B3
-    uint64_t first;          // row i is stream index first + i
-    uint32_t n;              // rows of this launch (<= 2^24)
-    uint32_t cap;            // a grid is kept iff its placements are <= cap
-    uint32_t hard;           // max(cap, kGenFloor): the fill stops before placement hard + 1
-    uint8_t* grids;          // uint8[n][81]
-    uint8_t* order;          // uint8[n][81], nullable
-    uint32_t* placements;    // uint32[n], nullable
-    uint32_t* next;          // the dequeue counter (zeroed before the launch)
-};
 
 enum : uint32_t { kGenIdle = 0, kGenFill = 1, kGenOrder = 2, kGenFin = 3 };
 

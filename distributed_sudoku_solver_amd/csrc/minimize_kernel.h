@@ -23,24 +23,15 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-namespace sdk {
+#include "minimize_args.h"
 
-struct MinRoundArgs {
-    const uint8_t* src;      // launch 0: the input boards; later: cur
-    uint8_t* cur;            // the boards so far (the call's `out`)
-    uint8_t* cand;           // round q's candidates (null at q = 81)
-    const uint8_t* order;    // uint8[n][81]
-    const int8_t* status;    // the inputs' verdicts
-    const int8_t* cst;       // round q - 1's candidate verdicts (unread at q = 0)
-    uint64_t n;
-    uint32_t q;              // 0..81
-};
+namespace sdk {
 
 __device__ __forceinline__ uint32_t min_refuted_cell(uint32_t c) {
     return c < 8u ? c + 1u : (c == 17u ? 9u : 0u);
 }
 
-__global__ __launch_bounds__(256) void minimize_round_kernel(MinRoundArgs a) {
+__global__ __launch_bounds__(kMinThreads) void minimize_round_kernel(MinRoundArgs a) {
     const uint64_t total = a.n * 81u;
     const uint64_t stride = 4ull * gridDim.x * blockDim.x;
     for (uint64_t e0 = 4ull * ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x); e0 < total; e0 += stride) {

@@ -1,5 +1,6 @@
 // sudoku_hip.hip -- libsudoku_hip.so: C-ABI (include/sudoku_hip.h) over the gfx950 kernels.
 //
+// Plain C++ (the Makefile compiles it with no device pass): the kernels are behind launch.h.
 // Host side is deliberately thin: a context = (device, stream, grow-only device
 // workspaces, HIP event pairs for kernel timing, options) behind a mutex.  No
 // CPU compute path exists: every board is checked / solved by a HIP kernel.
@@ -18,13 +19,7 @@
 #include <vector>
 
 #include "../../include/sudoku_hip.h"
-#include "launch.h"   // the solve, prop32 and grade32 kernels: their units' launch functions and *_args.h
-// the kernels this unit still compiles itself
-#include "check_kernel.h"
-#include "frontier_kernel.h"
-#include "minimize_kernel.h"
-#include "generate_kernel.h"
-#include "solve_lane_kernel.h"
+#include "launch.h"   // every kernel: its unit's launch functions and *_args.h (this file is plain C++)
 
 namespace {
 
@@ -108,203 +103,6 @@ int check_order_rows(const uint8_t* order, size_t n) {
 int64_t budget_arg(uint64_t node_budget) { return node_budget == SDK_BUDGET_CONTEXT ? -1 : (int64_t)node_budget; }
 
 }  // namespace
-
-namespace sdk {
-// two-phase solve (launch_solve): list the split phase's budget hits, gather them into a
-// dense batch, scatter their answers back
-// A list is a length word and the board indices after it; its length is read on the device
-// (the phases are enqueued without the host).  Collecting a board also copies it (and its
-// first-cell mask) to the list's position in the next phase's dense input: the boards
-// listed are a launch's tail, a few per thousand, so one thread per board does.  n_dev
-// (nullable) bounds n by an earlier list.
-// Resuming (`save` non-null, the split phase's list): a board whose stack the split phase left
-// (SplitSave, validated by its header) goes to the seed list instead -- (board, save entry)
-// pairs after a length word, with the words the records and items it needs reserved in the
-// donation area's DnSeed -- and dn_seed_kernel lists it after the restarted ones; `rcount`
-// counts the restarted boards alone (the donation launch's dequeue).
-struct DnResume {
-    const SplitSave* save;
-    const uint32_t* save_idx;
-    DnCtl* ctl;
-    uint32_t* seeds;          // [0] seeded boards, [1] restarted boards, then (board, entry) pairs
-};
-__global__ void dn_collect_kernel(const int8_t* status, uint64_t n, const uint32_t* n_dev, int8_t code,
-                                  uint32_t* list, uint32_t* total, const uint8_t* in, const uint16_t* mask,
-                                  uint64_t in_first, uint64_t in_step, uint8_t* out, uint16_t* out_mask, DnResume rs) {
-    if (n_dev) n = min<uint64_t>(n, *n_dev);
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x)
-        if (status[i] == code) {
-            if (rs.save) {
-                const uint32_t e = rs.save_idx[i];
-                if (e < min(rs.save->count, kSaveCap) && rs.save->hdr[e].x == (uint32_t)i) {
-                    // items: the deepest level's current digit and every level's untried ones
-                    const uint32_t depth = rs.save->hdr[e].y;
-                    uint32_t items = 1;
-                    for (uint32_t l = 0; l < depth; ++l) items += (uint32_t)__popc(rs.save->lv[e][l][0].y >> 23);
-                    // reserve a board slot, then the items by compare-and-swap: a reservation is
-                    // committed only when it fits, and a board whose items do not fit gives its
-                    // slot back -- one deep stack does not use up the room of later small ones
-                    // (two unconditional adds consumed both on a failed reservation)
-                    bool fits = false;
-                    if (atomicAdd(&rs.ctl->seed.res_boards, 1u) < kSeedBoards) {
-                        uint32_t cur = __hip_atomic_load(&rs.ctl->seed.res_items, __ATOMIC_RELAXED,
-                                                         __HIP_MEMORY_SCOPE_AGENT);
-                        while (cur + items <= kSeedItems) {
-                            const uint32_t prev = atomicCAS(&rs.ctl->seed.res_items, cur, cur + items);
-                            if (prev == cur) {
-                                fits = true;
-                                break;
-                            }
-                            cur = prev;
-                        }
-                    }
-                    if (!fits) atomicSub(&rs.ctl->seed.res_boards, 1u);
-                    if (fits) {
-                        const uint32_t s = atomicAdd(rs.seeds, 1u);
-                        rs.seeds[2 + 2 * s] = (uint32_t)i;
-                        rs.seeds[3 + 2 * s] = e;
-                        continue;
-                    }
-                }
-                atomicAdd(rs.seeds + 1, 1u);
-            }
-            const uint32_t k = atomicAdd(list, 1u);
-            list[1 + k] = (uint32_t)i;
-            atomicAdd(total, 1u);
-            const uint8_t* src = in + (in_first + i * in_step) * 81;
-            uint8_t* dst = out + (uint64_t)k * 81;
-            for (int j = 0; j < 81; ++j) dst[j] = src[j];
-            if (mask) out_mask[k] = mask[i];
-        }
-}
-// A phased solve's control words, zeroed in one launch before its first phase: the split
-// phase's dequeue counter and heads, the statistics, both donation launches' control blocks
-// (their epochs set) and list lengths.
-struct DnPrep {
-    uint32_t* counter;
-    uint32_t* heads;
-    uint32_t heads_words;
-    uint32_t* stat;
-    uint32_t* ctl[2];
-    uint32_t epoch[2];
-    uint32_t fault;      // DnCtl.fault (SDK_OPT_DN_FAULT, test only)
-    uint32_t helpers;    // DnCtl.helpers (SDK_OPT_DONATE_HELPERS)
-    uint32_t* list[2];
-    uint32_t* seeds;     // the seed list's two length words (nullable)
-    uint32_t* save;      // SplitSave::count (nullable)
-};
-__global__ void dn_prep_kernel(DnPrep p) {
-    const uint32_t t = threadIdx.x;
-    if (t == 0) {
-        p.counter[0] = 0;
-        p.list[0][0] = 0;
-        p.list[1][0] = 0;
-        if (p.seeds) p.seeds[0] = p.seeds[1] = 0;
-        if (p.save) p.save[0] = 0;
-    }
-    if (p.stat && t < 2) p.stat[t] = 0;
-    if (p.heads)
-        for (uint32_t i = t; i < p.heads_words; i += blockDim.x) p.heads[i] = 0;
-    // every word but the sticky error word (the host reads and clears it after the solve)
-    constexpr uint32_t kEpoch = offsetof(DnCtl, epoch) / 4, kErr = offsetof(DnCtl, err) / 4,
-                       kFault = offsetof(DnCtl, fault) / 4, kHelpers = offsetof(DnCtl, helpers) / 4;
-    for (int k = 0; k < 2; ++k)
-        for (uint32_t i = t; i < sizeof(DnCtl) / 4; i += blockDim.x)
-            if (i != kErr)
-                p.ctl[k][i] = i == kEpoch ? p.epoch[k] : (i == kFault ? p.fault : (i == kHelpers ? p.helpers : 0u));
-}
-// The resumed boards (dn_collect_kernel's seed list), one workgroup of 64 each: listed after the
-// restarted boards (input and mask copied to the dense batch like theirs), a board record with
-// one open part per item, and the items -- each level's snapshot with its branch cell set to
-// one open digit (the deepest level: also the digit it was searching) -- appended to the
-// seed queue, shallowest level first (the largest subtrees start first).
-__global__ void dn_seed_kernel(const uint32_t* seeds, const SplitSave* save, uint32_t* list, uint32_t* total,
-                               const uint8_t* in, const uint16_t* mask, uint64_t in_first, uint64_t in_step,
-                               uint8_t* out, uint16_t* out_mask, DnCtl* ctl) {
-    __shared__ uint32_t sh[4];
-    const uint32_t t = threadIdx.x;
-    DnRec* recs = reinterpret_cast<DnRec*>(reinterpret_cast<char*>(ctl) + kDnRecOffset);
-    DnItem* items = reinterpret_cast<DnItem*>(reinterpret_cast<char*>(ctl) + kDnItemOffset);
-    uint32_t* seedq = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(ctl) + kDnSeedQOffset);
-    const uint32_t ns = min(seeds[0], kSeedBoards);
-    for (uint32_t s = blockIdx.x; s < ns; s += gridDim.x) {
-        const uint32_t i = seeds[2 + 2 * s], e = seeds[3 + 2 * s];
-        const uint32_t depth = save->hdr[e].y;
-        uint32_t nit = 1;
-        for (uint32_t l = 0; l < depth; ++l) nit += (uint32_t)__popc(save->lv[e][l][0].y >> 23);
-        if (t == 0) {
-            sh[0] = atomicAdd(list, 1u);
-            sh[1] = atomicAdd(&ctl->nrec, 1u);
-            sh[2] = atomicAdd(&ctl->item_alloc, nit);
-            sh[3] = atomicAdd(&ctl->seed.total, nit);
-            atomicAdd(total, 1u);
-        }
-        __syncthreads();
-        const uint32_t k = sh[0], r = sh[1], i0 = sh[2], q0 = sh[3];
-        if (t == 0) list[1 + k] = i;
-        const uint8_t* src = in + (in_first + (uint64_t)i * in_step) * 81;
-        for (uint32_t j = t; j < 81; j += blockDim.x) out[(uint64_t)k * 81 + j] = src[j];
-        if (t == 0 && mask) out_mask[k] = mask[i];
-        DnRec* R = recs + r;
-        if (t == 0) {
-            R->board = k;
-            R->open = nit;
-            R->nhit = R->flags = R->maxd = R->lock = R->version = R->have = 0;
-            R->work = 0;
-            R->total = 0;
-            R->first = kDnNone;
-        }
-        if (t < (uint32_t)kDnList) R->hit[t] = kDnNone;
-        // lane t < 27 of the half owns cells t, t + 27, t + 54: one snapshot word each
-        uint32_t q = 0;
-        for (uint32_t l = 0; l < depth; ++l) {
-            const uint2 hw = save->lv[e][l][0];
-            const uint32_t rec = hw.y >> 16, cell = rec & 0x7Fu;
-            uint32_t digits = rec >> 7;
-            if (l + 1 == depth) {
-                // the digit being searched: the highest one taken (digits go in ascending order)
-                const uint2 cw = save->lv[e][l][cell % 27];
-                const uint32_t third = cell / 27;
-                const uint32_t xc = (third == 0 ? cw.x : (third == 1 ? cw.x >> 16 : cw.y)) & 0x1FFu;
-                const uint32_t taken = xc & ~digits;
-                if (taken) digits |= 1u << (31 - __clz(taken));
-            }
-            const uint2 v = t < 27 ? save->lv[e][l][t] : make_uint2(0, 0);
-            const uint32_t y0 = v.x & 0xFFFFu, y1 = v.x >> 16, y2 = v.y & 0xFFFFu;
-            const bool k0 = cell == t, k1 = cell == t + 27, k2 = cell == t + 54;
-            for (uint32_t g = digits; g; g &= g - 1u, ++q) {
-                const uint32_t dv = (g & (0u - g)) | 0x400u;
-                DnItem* it = items + i0 + q;
-                if (t < 27) it->w[t] = make_uint2((k0 ? dv : y0) | ((k1 ? dv : y1) << 16), k2 ? dv : y2);
-                if (t == 0) {
-                    it->board = k;
-                    it->rec = r;
-                    it->plen = cell + 1u;
-                    seedq[q0 + q] = i0 + q;
-                }
-            }
-        }
-        if (t == 0) {
-            if (q != nit) atomicOr(&ctl->err, kDnErrSeed);   // the reservation and the items disagree
-            atomicAdd(&ctl->seed.boards, 1u);
-        }
-        __syncthreads();
-    }
-}
-__global__ void dn_scatter_kernel(const uint32_t* list, const uint8_t* sub_out, const int8_t* sub_st,
-                                  const uint64_t* sub_work, bool depth, uint8_t* out, int8_t* status, uint64_t* work) {
-    const uint32_t m = list[0];
-    const uint32_t* hits = list + 1;
-    for (uint32_t i = blockIdx.x; i < m; i += gridDim.x) {
-        const uint64_t j = hits[i];
-        if (threadIdx.x < 81) out[j * 81 + threadIdx.x] = sub_out[(uint64_t)i * 81 + threadIdx.x];
-        if (threadIdx.x == 0) {
-            status[j] = sub_st[i];
-            if (work && sub_work) work[j] = depth ? max(work[j], sub_work[i]) : work[j] + sub_work[i];
-        }
-    }
-}
-}  // namespace sdk
 
 // Pinned host staging of the host-pointer calls (Staging below): the
 // caller's arrays are copied into it on the CPU and moved by true asynchronous DMA.  HIP's own path
@@ -512,14 +310,14 @@ struct Piece {
 };
 
 // The copies of a host-pointer call: send() before the launch, fetch() after it (it synchronizes).
-// The (at most seven) pieces lie in the pinned area (HostBuf) in the order given -- widest element
+// The (at most eight) pieces lie in the pinned area (HostBuf) in the order given -- widest element
 // type first, so every slot is aligned for its type; a call too large for the area copies straight
 // from / to the caller's pageable memory.  An error return between send() and the end of fetch()
 // may leave copies from / into the area queued, so the stream is drained first: the next call's
 // memcpy into the area (or a grow that frees it) cannot race them.
 class Staging {
     sdk_ctx* c;
-    Piece p[7];
+    Piece p[8];
     int np = 0;
     bool armed = true;
 
@@ -602,16 +400,7 @@ int launch_check(sdk_ctx* c, const uint8_t* d_in, uint8_t* d_out, size_t n) {
     if (rc) return rc;
     int variant = c->check_variant;
     if (variant == SDK_CHECK_REG2 && tiles < 2ull * grid) variant = SDK_CHECK_REG1;   // rr2 needs a full tile per slot
-    switch (variant) {
-        case SDK_CHECK_REG2: sdk::check_kernel_rr2<<<grid, sdk::kCheckThreads, 0, c->stream>>>(d_in, d_out, (uint64_t)n); break;
-        case SDK_CHECK_GLDS2: sdk::check_kernel_glds<2><<<grid, sdk::kCheckThreads, 0, c->stream>>>(d_in, d_out, (uint64_t)n); break;
-        case SDK_CHECK_GLDS3: sdk::check_kernel_glds<3><<<grid, sdk::kCheckThreads, 0, c->stream>>>(d_in, d_out, (uint64_t)n); break;
-        case SDK_CHECK_GLDS4: sdk::check_kernel_glds<4><<<grid, sdk::kCheckThreads, 0, c->stream>>>(d_in, d_out, (uint64_t)n); break;
-        case SDK_CHECK_WAVE1: sdk::check_kernel_wave<1><<<grid, sdk::kCheckThreads, 0, c->stream>>>(d_in, d_out, (uint64_t)n); break;
-        case SDK_CHECK_WAVE2: sdk::check_kernel_wave<2><<<grid, sdk::kCheckThreads, 0, c->stream>>>(d_in, d_out, (uint64_t)n); break;
-        default: sdk::check_kernel<<<grid, sdk::kCheckThreads, 0, c->stream>>>(d_in, d_out, (uint64_t)n); break;
-    }
-    HIPCALL(hipGetLastError());
+    HIPCALL(sdk::launch_check(variant, d_in, d_out, (uint64_t)n, grid, c->stream));
     if ((rc = timer_end(c, stop))) return rc;
     return SDK_OK;
 }
@@ -649,8 +438,7 @@ int launch_solve_once(sdk_ctx* c, const SolveCall& s, const SolvePhase& ph = {})
         HIPCALL(hipMemsetAsync(c->counter.p, 0, 8, c->stream));
         a.next = static_cast<uint32_t*>(c->counter.p);
         if ((rc = timer_begin(c, &stop))) return rc;
-        sdk::solve_lane_kernel<<<grid_for(c, n, sdk::kLaneThreads, 6), sdk::kLaneThreads, 0, c->stream>>>(a);
-        HIPCALL(hipGetLastError());
+        HIPCALL(sdk::launch_solve_lane(a, grid_for(c, n, sdk::kLaneThreads, 6), c->stream));
         return timer_end(c, stop);
     }
     // two (solve2_kernel) or four (solve4_kernel) boards per wave for solves; count mode stays
@@ -798,15 +586,11 @@ int dn_collect(sdk_ctx* c, const SolveCall& from, int8_t code, int k, bool resum
     uint32_t* total = static_cast<uint32_t*>(c->dn_stat.p) + k;
     uint8_t* bin = static_cast<uint8_t*>(t.in.p);
     uint16_t* bmask = static_cast<uint16_t*>(from.mask ? t.mask.p : nullptr);
-    sdk::dn_collect_kernel<<<grid_for(c, from.n, 256, 8), 256, 0, c->stream>>>(
-        from.status, from.n, from.n_dev, code, lst, total, from.in, from.mask, from.in_first, from.in_step, bin, bmask,
-        rs);
-    HIPCALL(hipGetLastError());
-    if (resume) {
-        sdk::dn_seed_kernel<<<grid_for(c, sdk::kSeedBoards, 1, 4), 64, 0, c->stream>>>(
-            rs.seeds, rs.save, lst, total, from.in, from.mask, from.in_first, from.in_step, bin, bmask, rs.ctl);
-        HIPCALL(hipGetLastError());
-    }
+    HIPCALL(sdk::launch_dn_collect(from.status, from.n, from.n_dev, code, lst, total, from.in, from.mask, from.in_first,
+                                   from.in_step, bin, bmask, rs, grid_for(c, from.n, 256, 8), c->stream));
+    if (resume)
+        HIPCALL(sdk::launch_dn_seed(rs.seeds, rs.save, lst, total, from.in, from.mask, from.in_first, from.in_step, bin,
+                                    bmask, rs.ctl, grid_for(c, sdk::kSeedBoards, 1, 4), c->stream));
     return SDK_OK;
 }
 
@@ -836,9 +620,8 @@ int dn_resolve(sdk_ctx* c, const SolveCall& to, int k, int order, const uint32_t
             (rc = dn_resolve(c, sub, 1, SDK_ORDER_LEX)))
             return rc;
     }
-    sdk::dn_scatter_kernel<<<grid_for(c, to.n, 1, 16), 128, 0, c->stream>>>(
-        lst, sub.out, sub.status, sub.work, c->work_rounds == SDK_WORK_DEPTH, to.out, to.status, to.work);
-    HIPCALL(hipGetLastError());
+    HIPCALL(sdk::launch_dn_scatter(lst, sub.out, sub.status, sub.work, c->work_rounds == SDK_WORK_DEPTH, to.out,
+                                   to.status, to.work, grid_for(c, to.n, 1, 16), c->stream));
     return SDK_OK;
 }
 
@@ -876,8 +659,7 @@ int dn_prep(sdk_ctx* c, uint64_t cap, bool first_pass, bool resume) {
         p.seeds = static_cast<uint32_t*>(c->dn_seeds.p);
         p.save = static_cast<uint32_t*>(c->dn_save.p);
     }
-    sdk::dn_prep_kernel<<<1, 256, 0, c->stream>>>(p);
-    HIPCALL(hipGetLastError());
+    HIPCALL(sdk::launch_dn_prep(p, c->stream));
     return SDK_OK;
 }
 
@@ -1096,10 +878,18 @@ int launch_classify(sdk_ctx* c, const uint8_t* d_in, uint8_t* d_out, int8_t* d_s
 // the same work items -- the slice's counts filled with SDK_SUBSETS_NONE, the same counter cleared, one
 // half-wave per level-4 board of the list.  It reads the parents only.  Without the pointer nothing of
 // it is enqueued.
-int launch_grade(sdk_ctx* c, const uint8_t* d_in, uint8_t* d_out, int8_t* d_status, uint8_t* d_level, uint8_t* d_open,
-                 size_t n, int64_t budget, uint8_t* d_bd = nullptr, uint8_t* d_key = nullptr,
-                 uint8_t* d_open4 = nullptr) {
+// The columns of a grade call beside out and status, one byte per board: level always, the others nullable.
+struct GradeCols {
+    uint8_t *level, *open;
+    uint8_t *backdoors, *key;   // the rate stage (sdk_rate_batch)
+    uint8_t* open4;             // the subsets stage (sdk_subsets_batch)
+};
+
+int launch_grade(sdk_ctx* c, const uint8_t* d_in, uint8_t* d_out, int8_t* d_status, const GradeCols& cols, size_t n,
+                 int64_t budget) {
     if (n == 0) return SDK_OK;
+    uint8_t *const d_level = cols.level, *const d_open = cols.open, *const d_bd = cols.backdoors,
+                   *const d_key = cols.key, *const d_open4 = cols.open4;
     if ((reinterpret_cast<uintptr_t>(d_in) | reinterpret_cast<uintptr_t>(d_out)) & 15u)
         return fail(SDK_EINVAL, "device boards must be 16-byte aligned");
     if (budget < 0) budget = (int64_t)c->budget;
@@ -1196,15 +986,15 @@ int launch_minimize(sdk_ctx* c, const uint8_t* d_in, const uint8_t* d_order, uin
         a.status = d_status + b0;
         a.cst = cst;
         a.n = m;
-        const unsigned grid = grid_for(c, m * 81, 1024, 8);
+        const unsigned grid = grid_for(c, m * 81, sdk::kMinBlockBytes, 8);
         // the inputs' verdicts (the completions go to scratch: `out` starts as the inputs)
         rc = launch_classify(c, d_in + b0 * 81, scratch, d_status + b0, m, 0);
         for (uint32_t q = 0; q <= 81 && !rc; ++q) {
             a.src = q == 0 ? d_in + b0 * 81 : a.cur;
             a.cand = q < 81 ? cand : nullptr;
             a.q = q;
-            sdk::minimize_round_kernel<<<grid, 256, 0, c->stream>>>(a);
-            if (hipGetLastError() != hipSuccess) rc = fail(SDK_EHIP, "minimise round launch failed");
+            if (sdk::launch_minimize_round(a, grid, c->stream) != hipSuccess)
+                rc = fail(SDK_EHIP, "minimise round launch failed");
             if (!rc && q < 81) rc = launch_classify(c, cand, scratch, cst, m, 0);
         }
     }
@@ -1235,8 +1025,7 @@ int launch_generate(sdk_ctx* c, uint64_t seed, uint64_t first, size_t n, uint8_t
         a.placements = d_plc ? d_plc + b0 : nullptr;
         a.next = static_cast<uint32_t*>(c->counter.p);
         HIPCALL(hipMemsetAsync(c->counter.p, 0, 8, c->stream));
-        sdk::generate_kernel<<<grid_for(c, m, sdk::kGenThreads, sdk::kGenWavesPerCu), sdk::kGenThreads, 0, c->stream>>>(a);
-        HIPCALL(hipGetLastError());
+        HIPCALL(sdk::launch_generate_grids(a, grid_for(c, m, sdk::kGenThreads, sdk::kGenWavesPerCu), c->stream));
     }
     return span.end(SDK_OK);
 }
@@ -1493,8 +1282,8 @@ int launch_generate_graded(sdk_ctx* c, const GradedCall& g, uint64_t* found, uin
         uint8_t* level = static_cast<uint8_t*>(c->gg_level.p);
         uint8_t* open = static_cast<uint8_t*>(c->gg_open.p);
         if ((rc = launch_generate_puzzles(c, g.seed, g.first + done, m, puz, grid, st)) ||
-            (rc = launch_grade(c, puz, static_cast<uint8_t*>(c->gg_sol.p), static_cast<int8_t*>(c->gg_gst.p), level,
-                               open, m, 0, bd, key, o4)))
+            (rc = launch_grade(c, puz, static_cast<uint8_t*>(c->gg_sol.p), static_cast<int8_t*>(c->gg_gst.p),
+                               GradeCols{level, open, bd, key, o4}, m, 0)))
             return rc;
         SelectRound r{};
         r.puzzles = puz;
@@ -1566,6 +1355,129 @@ int check_subsets_range(uint32_t lo, uint32_t hi) {
     return SDK_OK;
 }
 
+uint8_t* u8(void* p) { return static_cast<uint8_t*>(p); }
+
+// sdk_grade_batch, sdk_rate_batch, sdk_subsets_batch and their _dev forms, behind each one's own test of
+// its required pointers: `cols` holds the columns the entry point has, the others null.  host: the pointers
+// are the caller's arrays, staged through the context's buffers (the same ones whichever family calls);
+// else they are device pointers and the call only enqueues.
+int grade_call(sdk_ctx* c, bool host, const void* in, void* out, void* status, const GradeCols& cols, size_t n,
+               uint64_t node_budget) {
+    int rc;
+    if ((rc = check_budget_arg(node_budget))) return rc;
+    if (n == 0) return SDK_OK;
+    if ((rc = check_board_count(n))) return rc;
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCALL(hipSetDevice(c->device));
+    if (!host)
+        return launch_grade(c, static_cast<const uint8_t*>(in), u8(out), static_cast<int8_t*>(status), cols, n,
+                            budget_arg(node_budget));
+    if ((rc = ensure(c->in, n * 81)) || (rc = ensure(c->out, n * 81)) || (rc = ensure(c->status, n)) ||
+        (rc = ensure(c->gr_level, n)) || (cols.open && (rc = ensure(c->gr_open, n))) ||
+        (cols.backdoors && (rc = ensure(c->rt_bd, n))) || (cols.key && (rc = ensure(c->rt_key, n))) ||
+        (cols.open4 && (rc = ensure(c->s4_open4, n))))
+        return rc;
+    uint8_t* d_in = u8(c->in.p);
+    uint8_t* d_out = u8(c->out.p);
+    int8_t* d_status = static_cast<int8_t*>(c->status.p);
+    const GradeCols d{u8(c->gr_level.p), cols.open ? u8(c->gr_open.p) : nullptr,
+                      cols.backdoors ? u8(c->rt_bd.p) : nullptr, cols.key ? u8(c->rt_key.p) : nullptr,
+                      cols.open4 ? u8(c->s4_open4.p) : nullptr};
+    // a column comes back iff the caller has it (a slot each, present or not)
+    auto column = [n](const uint8_t* dev, uint8_t* dst) { return Piece{dst ? n : 0, nullptr, nullptr, dev, dst}; };
+    Staging io(c, {{n * 81, in, d_in, d_out, out},
+                   {n, nullptr, nullptr, d_status, status},
+                   column(d.level, cols.level),
+                   column(d.open, cols.open),
+                   column(d.backdoors, cols.backdoors),
+                   column(d.key, cols.key),
+                   column(d.open4, cols.open4)});
+    if ((rc = io.send()) || (rc = launch_grade(c, d_in, d_out, d_status, d, n, budget_arg(node_budget)))) return rc;
+    return io.fetch();
+}
+
+// sdk_generate_graded, sdk_generate_rated, sdk_generate_subsets and their _dev forms: `g` is the call with
+// the caller's pointers (its n is set here, from the checked `n`).  host: they are host arrays, and the
+// rows found come back through the context's gg_out_* buffers; else they are device pointers.  The order
+// of the checks is the order of the errors a caller with several bad arguments sees.
+int graded_call(sdk_ctx* c, bool host, size_t n, GradedCall g, uint64_t* found, uint64_t* scanned) {
+    if (!c || !found || (n && (!g.puzzles || !g.grids))) return fail(SDK_EINVAL, "NULL argument");
+    int rc;
+    if ((rc = check_graded_args(g.first, n, g.level_mask, g.clues_lo, g.clues_hi, g.max_scan, g.chunk)) ||
+        (g.rated && (rc = check_rated_range(g.bd_lo, g.bd_hi))) ||
+        (g.subsets && (rc = check_subsets_range(g.o4_lo, g.o4_hi))))
+        return rc;
+    if (!host) {
+        if ((reinterpret_cast<uintptr_t>(g.puzzles) | reinterpret_cast<uintptr_t>(g.grids)) & 15u)
+            return fail(SDK_EINVAL, "device boards must be 16-byte aligned");
+        if (reinterpret_cast<uintptr_t>(g.index) & 7u) return fail(SDK_EINVAL, "d_index must be 8-byte aligned");
+    }
+    g.n = (uint32_t)n;
+    uint64_t f = 0, s = 0;
+    if (n) {
+        std::lock_guard<std::mutex> lk(c->mu);
+        HIPCALL(hipSetDevice(c->device));
+        GradedCall d = g;   // the call on device pointers
+        if (host) {
+            // at most min(n, max_scan) rows can come back
+            const size_t rows = (size_t)std::min<uint64_t>(n, g.max_scan);
+            if ((rc = ensure(c->gg_out_puz, rows * 81)) || (rc = ensure(c->gg_out_grid, rows * 81)) ||
+                (g.level && (rc = ensure(c->gg_out_level, rows))) || (g.open && (rc = ensure(c->gg_out_open, rows))) ||
+                (g.backdoors && (rc = ensure(c->gg_out_bd, rows))) || (g.key && (rc = ensure(c->gg_out_key, rows))) ||
+                (g.open4 && (rc = ensure(c->gg_out_o4, rows))) || (g.index && (rc = ensure(c->gg_out_index, rows * 8))))
+                return rc;
+            d.puzzles = u8(c->gg_out_puz.p);
+            d.grids = u8(c->gg_out_grid.p);
+            d.level = g.level ? u8(c->gg_out_level.p) : nullptr;
+            d.open = g.open ? u8(c->gg_out_open.p) : nullptr;
+            d.backdoors = g.backdoors ? u8(c->gg_out_bd.p) : nullptr;
+            d.key = g.key ? u8(c->gg_out_key.p) : nullptr;
+            d.open4 = g.open4 ? u8(c->gg_out_o4.p) : nullptr;
+            d.index = g.index ? static_cast<uint64_t*>(c->gg_out_index.p) : nullptr;
+        }
+        if ((rc = launch_generate_graded(c, d, &f, &s))) return rc;
+        if (host && f) {
+            // the rows found, and nothing behind them
+            auto column = [f](const uint8_t* dev, uint8_t* dst) { return Piece{dst ? f : 0, nullptr, nullptr, dev, dst}; };
+            Staging io(c, {{g.index ? f * 8 : 0, nullptr, nullptr, d.index, g.index},
+                           {f * 81, nullptr, nullptr, d.puzzles, g.puzzles},
+                           {f * 81, nullptr, nullptr, d.grids, g.grids},
+                           column(d.level, g.level),
+                           column(d.open, g.open),
+                           column(d.backdoors, g.backdoors),
+                           column(d.key, g.key),
+                           column(d.open4, g.open4)});
+            if ((rc = io.fetch())) return rc;
+        }
+    }
+    *found = f;
+    if (scanned) *scanned = s;
+    return SDK_OK;
+}
+
+// the arguments every graded family has, as a call without a stage
+GradedCall graded_args(uint64_t seed, uint64_t first, uint32_t level_mask, uint32_t clues_lo, uint32_t clues_hi,
+                       uint64_t max_scan, uint64_t chunk, void* puzzles, void* grids, void* level, void* open,
+                       void* index) {
+    return GradedCall{seed, first, 0, level_mask, clues_lo, clues_hi, max_scan, chunk, u8(puzzles), u8(grids),
+                      u8(level), u8(open), static_cast<uint64_t*>(index)};
+}
+GradedCall rated_args(GradedCall g, uint32_t lo, uint32_t hi, void* backdoors, void* key) {
+    g.rated = true;
+    g.bd_lo = lo;
+    g.bd_hi = hi;
+    g.backdoors = u8(backdoors);
+    g.key = u8(key);
+    return g;
+}
+GradedCall subsets_args(GradedCall g, uint32_t lo, uint32_t hi, void* open4) {
+    g.subsets = true;
+    g.o4_lo = lo;
+    g.o4_hi = hi;
+    g.open4 = u8(open4);
+    return g;
+}
+
 // Deterministic breadth-first frontier of one board, left in c->fr_a.
 // Every rank that builds it from the same board gets the same boards in the same
 // order, so ranks can split it without exchanging boards.
@@ -1618,7 +1530,7 @@ int run_frontier_levels(sdk_ctx* c, uint64_t m0, bool use_mask, int mode, uint64
     constexpr int kLevelsPerSync = 4;
     for (int level = 0; level < 81; ++level) {
         const int in = level & 1;
-        sdk::frontier_begin_kernel<<<1, 1, 0, c->stream>>>(ctl, target, level == 0 && force0 ? 1 : 0);
+        HIPCALL(sdk::launch_frontier_begin(ctl, target, level == 0 && force0 ? 1 : 0, c->stream));
         sdk::ExpandArgs ea;
         ea.in = static_cast<const uint8_t*>(buf[in]);
         ea.ctl = ctl;
@@ -1632,17 +1544,14 @@ int run_frontier_levels(sdk_ctx* c, uint64_t m0, bool use_mask, int mode, uint64
         if (quad)   // four boards per wave (expand4_kernel.h): the same frontier, byte for byte
             HIPCALL(sdk::launch_expand4(ea, eg4, c->stream));
         else
-            sdk::expand_kernel<<<eg, 64, 0, c->stream>>>(ea);
-        sdk::scan_tiles_kernel<<<sg, 1024, 0, c->stream>>>(static_cast<uint32_t*>(c->nchild.p),
-                                                           static_cast<uint64_t*>(c->offs.p), ctl,
-                                                           static_cast<uint64_t*>(c->tsum.p));
-        sdk::scan_top_kernel<<<1, 1024, 0, c->stream>>>(static_cast<uint64_t*>(c->tsum.p), ctl, c_out);
-        sdk::emit_kernel<<<gg, 64, 0, c->stream>>>(static_cast<uint8_t*>(c->prop.p), static_cast<uint8_t*>(c->bcell.p),
-                                                   static_cast<uint16_t*>(c->bmask.p), static_cast<uint64_t*>(c->offs.p),
-                                                   static_cast<uint64_t*>(c->tsum.p), ctl,
-                                                   static_cast<uint8_t*>(buf[in ^ 1]));
-        sdk::frontier_end_kernel<<<1, 1, 0, c->stream>>>(ctl, first ? 1 : 0);
-        HIPCALL(hipGetLastError());
+            HIPCALL(sdk::launch_expand(ea, eg, c->stream));
+        uint64_t* offs = static_cast<uint64_t*>(c->offs.p);
+        uint64_t* tsum = static_cast<uint64_t*>(c->tsum.p);
+        HIPCALL(sdk::launch_scan_tiles(ea.nchild, offs, ctl, tsum, sg, c->stream));
+        HIPCALL(sdk::launch_scan_top(tsum, ctl, c_out, c->stream));
+        HIPCALL(sdk::launch_emit(ea.prop, ea.bcell, ea.bmask, offs, tsum, ctl, static_cast<uint8_t*>(buf[in ^ 1]), gg,
+                                 c->stream));
+        HIPCALL(sdk::launch_frontier_end(ctl, first ? 1 : 0, c->stream));
         if (level % kLevelsPerSync == kLevelsPerSync - 1 || level == 80) {
             HIPCALL(hipMemcpyAsync(&h, ctl, sizeof h, hipMemcpyDeviceToHost, c->stream));
             HIPCALL(hipStreamSynchronize(c->stream));
@@ -1687,9 +1596,8 @@ int refine_frontier(sdk_ctx* c, uint64_t first, uint64_t step, uint64_t end, uin
     // fr_b takes the share and becomes fr_a: size it for the whole refinement now
     if ((rc = ensure(c->fr_b, frontier_capacity(std::max<uint64_t>(n, 1), target) * 81))) return rc;
     if (n) {
-        sdk::gather_boards_kernel<<<grid_for(c, n, 4, 16), 256, 0, c->stream>>>(
-            static_cast<const uint8_t*>(c->fr_a.p), first, step, n, static_cast<uint8_t*>(c->fr_b.p));
-        HIPCALL(hipGetLastError());
+        HIPCALL(sdk::launch_gather_boards(static_cast<const uint8_t*>(c->fr_a.p), first, step, n,
+                                          static_cast<uint8_t*>(c->fr_b.p), grid_for(c, n, 4, 16), c->stream));
     }
     std::swap(c->fr_a, c->fr_b);
     if (n == 0) {
@@ -1792,8 +1700,7 @@ int frontier_count(sdk_ctx* c, uint64_t first, uint64_t step, uint64_t end, uint
         s.count = d_count;
         if ((rc = launch_solve(c, s))) return rc;
     }
-    sdk::count_result_kernel<<<1, 256, 0, c->stream>>>(static_cast<int8_t*>(c->fr_status.p), n, d_count, d_result);
-    HIPCALL(hipGetLastError());
+    HIPCALL(sdk::launch_count_result(static_cast<int8_t*>(c->fr_status.p), n, d_count, d_result, c->stream));
     return SDK_OK;
 }
 
@@ -1810,8 +1717,7 @@ int frontier_first(sdk_ctx* c, uint64_t lo, uint64_t hi, long long* d_found, uin
         // boards above the lowest hit are cancelled inside the launch (solve4_kernel<.., FS>):
         // d_found is its found word until first_hit_kernel writes the answer.  The plain kernel
         // (no subtree donation: a heavy board is split by the caller, shard.sharded_solve)
-        sdk::first_init_kernel<<<1, 1, 0, c->stream>>>(d_found);
-        HIPCALL(hipGetLastError());
+        HIPCALL(sdk::launch_first_init(d_found, c->stream));
         SolveCall s{static_cast<uint8_t*>(c->fr_a.p), nullptr, static_cast<uint8_t*>(c->out.p),
                     static_cast<int8_t*>(c->status.p), nullptr, n};
         s.in_first = lo;
@@ -1819,9 +1725,8 @@ int frontier_first(sdk_ctx* c, uint64_t lo, uint64_t hi, long long* d_found, uin
         s.found = d_found;
         if ((rc = launch_solve(c, s))) return rc;
     }
-    sdk::first_hit_kernel<<<1, 256, 0, c->stream>>>(static_cast<int8_t*>(c->status.p),
-                                                    static_cast<uint8_t*>(c->out.p), n, lo, d_found, d_best);
-    HIPCALL(hipGetLastError());
+    HIPCALL(sdk::launch_first_hit(static_cast<int8_t*>(c->status.p), static_cast<uint8_t*>(c->out.p), n, lo, d_found,
+                                  d_best, c->stream));
     return SDK_OK;
 }
 
@@ -2299,9 +2204,8 @@ int sdk_check_batch_i64(sdk_ctx* c, const int64_t* boards, uint8_t* verdict, siz
     HIPCALL(hipMemcpyAsync(c->in.p, boards, n * 81 * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
     hipEvent_t stop;
     if ((rc = timer_begin(c, &stop))) return rc;
-    sdk::check_kernel_i64<<<grid_for(c, n, 256, 8), 256, 0, c->stream>>>(static_cast<const int64_t*>(c->in.p),
-                                                      static_cast<uint8_t*>(c->verdict.p), (uint64_t)n);
-    HIPCALL(hipGetLastError());
+    HIPCALL(sdk::launch_check_i64(static_cast<const int64_t*>(c->in.p), static_cast<uint8_t*>(c->verdict.p), (uint64_t)n,
+                                  grid_for(c, n, sdk::kCheckI64Threads, 8), c->stream));
     if ((rc = timer_end(c, stop))) return rc;
     HIPCALL(hipMemcpyAsync(verdict, c->verdict.p, n, hipMemcpyDeviceToHost, c->stream));
     HIPCALL(hipStreamSynchronize(c->stream));
@@ -2376,131 +2280,40 @@ int sdk_classify_batch(sdk_ctx* c, const uint8_t* in, uint8_t* out, int8_t* stat
 int sdk_grade_batch_dev(sdk_ctx* c, const void* d_in, void* d_out, void* d_status, void* d_level, void* d_open,
                         size_t n, uint64_t node_budget) {
     if (!c || (n && (!d_in || !d_out || !d_status || !d_level))) return fail(SDK_EINVAL, "NULL argument");
-    int rc;
-    if ((rc = check_budget_arg(node_budget))) return rc;
-    if (n == 0) return SDK_OK;
-    if ((rc = check_board_count(n))) return rc;
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIPCALL(hipSetDevice(c->device));
-    return launch_grade(c, static_cast<const uint8_t*>(d_in), static_cast<uint8_t*>(d_out),
-                        static_cast<int8_t*>(d_status), static_cast<uint8_t*>(d_level), static_cast<uint8_t*>(d_open),
-                        n, budget_arg(node_budget));
+    return grade_call(c, false, d_in, d_out, d_status, {u8(d_level), u8(d_open), nullptr, nullptr, nullptr}, n,
+                      node_budget);
 }
 
 int sdk_grade_batch(sdk_ctx* c, const uint8_t* in, uint8_t* out, int8_t* status, uint8_t* level, uint8_t* open,
                     size_t n, uint64_t node_budget) {
     if (!c || (n && (!in || !out || !status || !level))) return fail(SDK_EINVAL, "NULL argument");
-    int rc;
-    if ((rc = check_budget_arg(node_budget))) return rc;
-    if (n == 0) return SDK_OK;
-    if ((rc = check_board_count(n))) return rc;
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIPCALL(hipSetDevice(c->device));
-    if ((rc = ensure(c->in, n * 81)) || (rc = ensure(c->out, n * 81)) || (rc = ensure(c->status, n)) ||
-        (rc = ensure(c->gr_level, n)) || (open && (rc = ensure(c->gr_open, n))))
-        return rc;
-    uint8_t* d_in = static_cast<uint8_t*>(c->in.p);
-    uint8_t* d_out = static_cast<uint8_t*>(c->out.p);
-    int8_t* d_status = static_cast<int8_t*>(c->status.p);
-    uint8_t* d_level = static_cast<uint8_t*>(c->gr_level.p);
-    uint8_t* d_open = open ? static_cast<uint8_t*>(c->gr_open.p) : nullptr;
-    Staging io(c, {{n * 81, in, d_in, d_out, out},
-                   {n, nullptr, nullptr, d_status, status},
-                   {n, nullptr, nullptr, d_level, level},
-                   {open ? n : 0, nullptr, nullptr, d_open, open}});
-    if ((rc = io.send()) ||
-        (rc = launch_grade(c, d_in, d_out, d_status, d_level, d_open, n, budget_arg(node_budget))))
-        return rc;
-    return io.fetch();
+    return grade_call(c, true, in, out, status, {level, open, nullptr, nullptr, nullptr}, n, node_budget);
 }
 
 int sdk_rate_batch_dev(sdk_ctx* c, const void* d_in, void* d_out, void* d_status, void* d_level, void* d_open,
                        void* d_backdoors, void* d_key, size_t n, uint64_t node_budget) {
     if (!c || (n && (!d_in || !d_out || !d_status || !d_level || !d_backdoors))) return fail(SDK_EINVAL, "NULL argument");
-    int rc;
-    if ((rc = check_budget_arg(node_budget))) return rc;
-    if (n == 0) return SDK_OK;
-    if ((rc = check_board_count(n))) return rc;
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIPCALL(hipSetDevice(c->device));
-    return launch_grade(c, static_cast<const uint8_t*>(d_in), static_cast<uint8_t*>(d_out),
-                        static_cast<int8_t*>(d_status), static_cast<uint8_t*>(d_level), static_cast<uint8_t*>(d_open),
-                        n, budget_arg(node_budget), static_cast<uint8_t*>(d_backdoors), static_cast<uint8_t*>(d_key));
+    return grade_call(c, false, d_in, d_out, d_status, {u8(d_level), u8(d_open), u8(d_backdoors), u8(d_key), nullptr},
+                      n, node_budget);
 }
 
 int sdk_rate_batch(sdk_ctx* c, const uint8_t* in, uint8_t* out, int8_t* status, uint8_t* level, uint8_t* open,
                    uint8_t* backdoors, uint8_t* key, size_t n, uint64_t node_budget) {
     if (!c || (n && (!in || !out || !status || !level || !backdoors))) return fail(SDK_EINVAL, "NULL argument");
-    int rc;
-    if ((rc = check_budget_arg(node_budget))) return rc;
-    if (n == 0) return SDK_OK;
-    if ((rc = check_board_count(n))) return rc;
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIPCALL(hipSetDevice(c->device));
-    if ((rc = ensure(c->in, n * 81)) || (rc = ensure(c->out, n * 81)) || (rc = ensure(c->status, n)) ||
-        (rc = ensure(c->gr_level, n)) || (open && (rc = ensure(c->gr_open, n))) || (rc = ensure(c->rt_bd, n)) ||
-        (key && (rc = ensure(c->rt_key, n))))
-        return rc;
-    uint8_t* d_in = static_cast<uint8_t*>(c->in.p);
-    uint8_t* d_out = static_cast<uint8_t*>(c->out.p);
-    int8_t* d_status = static_cast<int8_t*>(c->status.p);
-    uint8_t* d_level = static_cast<uint8_t*>(c->gr_level.p);
-    uint8_t* d_open = open ? static_cast<uint8_t*>(c->gr_open.p) : nullptr;
-    uint8_t* d_bd = static_cast<uint8_t*>(c->rt_bd.p);
-    uint8_t* d_key = key ? static_cast<uint8_t*>(c->rt_key.p) : nullptr;
-    Staging io(c, {{n * 81, in, d_in, d_out, out},
-                   {n, nullptr, nullptr, d_status, status},
-                   {n, nullptr, nullptr, d_level, level},
-                   {open ? n : 0, nullptr, nullptr, d_open, open},
-                   {n, nullptr, nullptr, d_bd, backdoors},
-                   {key ? n : 0, nullptr, nullptr, d_key, key}});
-    if ((rc = io.send()) ||
-        (rc = launch_grade(c, d_in, d_out, d_status, d_level, d_open, n, budget_arg(node_budget), d_bd, d_key)))
-        return rc;
-    return io.fetch();
+    return grade_call(c, true, in, out, status, {level, open, backdoors, key, nullptr}, n, node_budget);
 }
 
 int sdk_subsets_batch_dev(sdk_ctx* c, const void* d_in, void* d_out, void* d_status, void* d_level, void* d_open,
                           void* d_open4, size_t n, uint64_t node_budget) {
     if (!c || (n && (!d_in || !d_out || !d_status || !d_level || !d_open4))) return fail(SDK_EINVAL, "NULL argument");
-    int rc;
-    if ((rc = check_budget_arg(node_budget))) return rc;
-    if (n == 0) return SDK_OK;
-    if ((rc = check_board_count(n))) return rc;
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIPCALL(hipSetDevice(c->device));
-    return launch_grade(c, static_cast<const uint8_t*>(d_in), static_cast<uint8_t*>(d_out),
-                        static_cast<int8_t*>(d_status), static_cast<uint8_t*>(d_level), static_cast<uint8_t*>(d_open),
-                        n, budget_arg(node_budget), nullptr, nullptr, static_cast<uint8_t*>(d_open4));
+    return grade_call(c, false, d_in, d_out, d_status, {u8(d_level), u8(d_open), nullptr, nullptr, u8(d_open4)}, n,
+                      node_budget);
 }
 
 int sdk_subsets_batch(sdk_ctx* c, const uint8_t* in, uint8_t* out, int8_t* status, uint8_t* level, uint8_t* open,
                       uint8_t* open4, size_t n, uint64_t node_budget) {
     if (!c || (n && (!in || !out || !status || !level || !open4))) return fail(SDK_EINVAL, "NULL argument");
-    int rc;
-    if ((rc = check_budget_arg(node_budget))) return rc;
-    if (n == 0) return SDK_OK;
-    if ((rc = check_board_count(n))) return rc;
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIPCALL(hipSetDevice(c->device));
-    if ((rc = ensure(c->in, n * 81)) || (rc = ensure(c->out, n * 81)) || (rc = ensure(c->status, n)) ||
-        (rc = ensure(c->gr_level, n)) || (open && (rc = ensure(c->gr_open, n))) || (rc = ensure(c->s4_open4, n)))
-        return rc;
-    uint8_t* d_in = static_cast<uint8_t*>(c->in.p);
-    uint8_t* d_out = static_cast<uint8_t*>(c->out.p);
-    int8_t* d_status = static_cast<int8_t*>(c->status.p);
-    uint8_t* d_level = static_cast<uint8_t*>(c->gr_level.p);
-    uint8_t* d_open = open ? static_cast<uint8_t*>(c->gr_open.p) : nullptr;
-    uint8_t* d_open4 = static_cast<uint8_t*>(c->s4_open4.p);
-    Staging io(c, {{n * 81, in, d_in, d_out, out},
-                   {n, nullptr, nullptr, d_status, status},
-                   {n, nullptr, nullptr, d_level, level},
-                   {open ? n : 0, nullptr, nullptr, d_open, open},
-                   {n, nullptr, nullptr, d_open4, open4}});
-    if ((rc = io.send()) || (rc = launch_grade(c, d_in, d_out, d_status, d_level, d_open, n, budget_arg(node_budget),
-                                               nullptr, nullptr, d_open4)))
-        return rc;
-    return io.fetch();
+    return grade_call(c, true, in, out, status, {level, open, nullptr, nullptr, open4}, n, node_budget);
 }
 
 int sdk_minimize_batch_dev(sdk_ctx* c, const void* d_in, const void* d_order, void* d_out, void* d_status, size_t n) {
@@ -2669,62 +2482,19 @@ int sdk_generate_graded_dev(sdk_ctx* c, uint64_t seed, uint64_t first, size_t n,
                             uint32_t clues_lo, uint32_t clues_hi, uint64_t max_scan, uint64_t chunk, void* d_puzzles,
                             void* d_grids, void* d_level, void* d_open, void* d_index, uint64_t* found,
                             uint64_t* scanned) {
-    if (!c || !found || (n && (!d_puzzles || !d_grids))) return fail(SDK_EINVAL, "NULL argument");
-    int rc;
-    if ((rc = check_graded_args(first, n, level_mask, clues_lo, clues_hi, max_scan, chunk))) return rc;
-    if ((reinterpret_cast<uintptr_t>(d_puzzles) | reinterpret_cast<uintptr_t>(d_grids)) & 15u)
-        return fail(SDK_EINVAL, "device boards must be 16-byte aligned");
-    if (reinterpret_cast<uintptr_t>(d_index) & 7u) return fail(SDK_EINVAL, "d_index must be 8-byte aligned");
-    uint64_t f = 0, s = 0;
-    if (n) {
-        std::lock_guard<std::mutex> lk(c->mu);
-        HIPCALL(hipSetDevice(c->device));
-        const GradedCall g{seed, first, (uint32_t)n, level_mask, clues_lo, clues_hi, max_scan, chunk,
-                           static_cast<uint8_t*>(d_puzzles), static_cast<uint8_t*>(d_grids),
-                           static_cast<uint8_t*>(d_level), static_cast<uint8_t*>(d_open),
-                           static_cast<uint64_t*>(d_index)};
-        if ((rc = launch_generate_graded(c, g, &f, &s))) return rc;
-    }
-    *found = f;
-    if (scanned) *scanned = s;
-    return SDK_OK;
+    return graded_call(c, false, n,
+                       graded_args(seed, first, level_mask, clues_lo, clues_hi, max_scan, chunk, d_puzzles, d_grids,
+                                   d_level, d_open, d_index),
+                       found, scanned);
 }
 
 int sdk_generate_graded(sdk_ctx* c, uint64_t seed, uint64_t first, size_t n, uint32_t level_mask, uint32_t clues_lo,
                         uint32_t clues_hi, uint64_t max_scan, uint64_t chunk, uint8_t* puzzles, uint8_t* grids,
                         uint8_t* level, uint8_t* open, uint64_t* index, uint64_t* found, uint64_t* scanned) {
-    if (!c || !found || (n && (!puzzles || !grids))) return fail(SDK_EINVAL, "NULL argument");
-    int rc;
-    if ((rc = check_graded_args(first, n, level_mask, clues_lo, clues_hi, max_scan, chunk))) return rc;
-    uint64_t f = 0, s = 0;
-    if (n) {
-        std::lock_guard<std::mutex> lk(c->mu);
-        HIPCALL(hipSetDevice(c->device));
-        // at most min(n, max_scan) rows can come back
-        const size_t rows = (size_t)std::min<uint64_t>(n, max_scan);
-        if ((rc = ensure(c->gg_out_puz, rows * 81)) || (rc = ensure(c->gg_out_grid, rows * 81)) ||
-            (level && (rc = ensure(c->gg_out_level, rows))) || (open && (rc = ensure(c->gg_out_open, rows))) ||
-            (index && (rc = ensure(c->gg_out_index, rows * 8))))
-            return rc;
-        const GradedCall g{seed, first, (uint32_t)n, level_mask, clues_lo, clues_hi, max_scan, chunk,
-                           static_cast<uint8_t*>(c->gg_out_puz.p), static_cast<uint8_t*>(c->gg_out_grid.p),
-                           level ? static_cast<uint8_t*>(c->gg_out_level.p) : nullptr,
-                           open ? static_cast<uint8_t*>(c->gg_out_open.p) : nullptr,
-                           index ? static_cast<uint64_t*>(c->gg_out_index.p) : nullptr};
-        if ((rc = launch_generate_graded(c, g, &f, &s))) return rc;
-        if (f) {
-            // the rows found, and nothing behind them
-            Staging io(c, {{index ? f * 8 : 0, nullptr, nullptr, g.index, index},
-                           {f * 81, nullptr, nullptr, g.puzzles, puzzles},
-                           {f * 81, nullptr, nullptr, g.grids, grids},
-                           {level ? f : 0, nullptr, nullptr, g.level, level},
-                           {open ? f : 0, nullptr, nullptr, g.open, open}});
-            if ((rc = io.fetch())) return rc;
-        }
-    }
-    *found = f;
-    if (scanned) *scanned = s;
-    return SDK_OK;
+    return graded_call(c, true, n,
+                       graded_args(seed, first, level_mask, clues_lo, clues_hi, max_scan, chunk, puzzles, grids, level,
+                                   open, index),
+                       found, scanned);
 }
 
 int sdk_generate_rated_dev(sdk_ctx* c, uint64_t seed, uint64_t first, size_t n, uint32_t level_mask,
@@ -2732,150 +2502,44 @@ int sdk_generate_rated_dev(sdk_ctx* c, uint64_t seed, uint64_t first, size_t n, 
                            uint64_t max_scan, uint64_t chunk, void* d_puzzles, void* d_grids, void* d_level,
                            void* d_open, void* d_backdoors, void* d_key, void* d_index, uint64_t* found,
                            uint64_t* scanned) {
-    if (!c || !found || (n && (!d_puzzles || !d_grids))) return fail(SDK_EINVAL, "NULL argument");
-    int rc;
-    if ((rc = check_graded_args(first, n, level_mask, clues_lo, clues_hi, max_scan, chunk)) ||
-        (rc = check_rated_range(backdoors_lo, backdoors_hi)))
-        return rc;
-    if ((reinterpret_cast<uintptr_t>(d_puzzles) | reinterpret_cast<uintptr_t>(d_grids)) & 15u)
-        return fail(SDK_EINVAL, "device boards must be 16-byte aligned");
-    if (reinterpret_cast<uintptr_t>(d_index) & 7u) return fail(SDK_EINVAL, "d_index must be 8-byte aligned");
-    uint64_t f = 0, s = 0;
-    if (n) {
-        std::lock_guard<std::mutex> lk(c->mu);
-        HIPCALL(hipSetDevice(c->device));
-        GradedCall g{seed, first, (uint32_t)n, level_mask, clues_lo, clues_hi, max_scan, chunk,
-                     static_cast<uint8_t*>(d_puzzles), static_cast<uint8_t*>(d_grids), static_cast<uint8_t*>(d_level),
-                     static_cast<uint8_t*>(d_open), static_cast<uint64_t*>(d_index)};
-        g.rated = true;
-        g.bd_lo = backdoors_lo;
-        g.bd_hi = backdoors_hi;
-        g.backdoors = static_cast<uint8_t*>(d_backdoors);
-        g.key = static_cast<uint8_t*>(d_key);
-        if ((rc = launch_generate_graded(c, g, &f, &s))) return rc;
-    }
-    *found = f;
-    if (scanned) *scanned = s;
-    return SDK_OK;
+    return graded_call(c, false, n,
+                       rated_args(graded_args(seed, first, level_mask, clues_lo, clues_hi, max_scan, chunk, d_puzzles,
+                                              d_grids, d_level, d_open, d_index),
+                                  backdoors_lo, backdoors_hi, d_backdoors, d_key),
+                       found, scanned);
 }
 
 int sdk_generate_rated(sdk_ctx* c, uint64_t seed, uint64_t first, size_t n, uint32_t level_mask, uint32_t clues_lo,
                        uint32_t clues_hi, uint32_t backdoors_lo, uint32_t backdoors_hi, uint64_t max_scan,
                        uint64_t chunk, uint8_t* puzzles, uint8_t* grids, uint8_t* level, uint8_t* open,
                        uint8_t* backdoors, uint8_t* key, uint64_t* index, uint64_t* found, uint64_t* scanned) {
-    if (!c || !found || (n && (!puzzles || !grids))) return fail(SDK_EINVAL, "NULL argument");
-    int rc;
-    if ((rc = check_graded_args(first, n, level_mask, clues_lo, clues_hi, max_scan, chunk)) ||
-        (rc = check_rated_range(backdoors_lo, backdoors_hi)))
-        return rc;
-    uint64_t f = 0, s = 0;
-    if (n) {
-        std::lock_guard<std::mutex> lk(c->mu);
-        HIPCALL(hipSetDevice(c->device));
-        const size_t rows = (size_t)std::min<uint64_t>(n, max_scan);
-        if ((rc = ensure(c->gg_out_puz, rows * 81)) || (rc = ensure(c->gg_out_grid, rows * 81)) ||
-            (level && (rc = ensure(c->gg_out_level, rows))) || (open && (rc = ensure(c->gg_out_open, rows))) ||
-            (backdoors && (rc = ensure(c->gg_out_bd, rows))) || (key && (rc = ensure(c->gg_out_key, rows))) ||
-            (index && (rc = ensure(c->gg_out_index, rows * 8))))
-            return rc;
-        GradedCall g{seed, first, (uint32_t)n, level_mask, clues_lo, clues_hi, max_scan, chunk,
-                     static_cast<uint8_t*>(c->gg_out_puz.p), static_cast<uint8_t*>(c->gg_out_grid.p),
-                     level ? static_cast<uint8_t*>(c->gg_out_level.p) : nullptr,
-                     open ? static_cast<uint8_t*>(c->gg_out_open.p) : nullptr,
-                     index ? static_cast<uint64_t*>(c->gg_out_index.p) : nullptr};
-        g.rated = true;
-        g.bd_lo = backdoors_lo;
-        g.bd_hi = backdoors_hi;
-        g.backdoors = backdoors ? static_cast<uint8_t*>(c->gg_out_bd.p) : nullptr;
-        g.key = key ? static_cast<uint8_t*>(c->gg_out_key.p) : nullptr;
-        if ((rc = launch_generate_graded(c, g, &f, &s))) return rc;
-        if (f) {
-            Staging io(c, {{index ? f * 8 : 0, nullptr, nullptr, g.index, index},
-                           {f * 81, nullptr, nullptr, g.puzzles, puzzles},
-                           {f * 81, nullptr, nullptr, g.grids, grids},
-                           {level ? f : 0, nullptr, nullptr, g.level, level},
-                           {open ? f : 0, nullptr, nullptr, g.open, open},
-                           {backdoors ? f : 0, nullptr, nullptr, g.backdoors, backdoors},
-                           {key ? f : 0, nullptr, nullptr, g.key, key}});
-            if ((rc = io.fetch())) return rc;
-        }
-    }
-    *found = f;
-    if (scanned) *scanned = s;
-    return SDK_OK;
+    return graded_call(c, true, n,
+                       rated_args(graded_args(seed, first, level_mask, clues_lo, clues_hi, max_scan, chunk, puzzles,
+                                              grids, level, open, index),
+                                  backdoors_lo, backdoors_hi, backdoors, key),
+                       found, scanned);
 }
 
 int sdk_generate_subsets_dev(sdk_ctx* c, uint64_t seed, uint64_t first, size_t n, uint32_t level_mask,
                              uint32_t clues_lo, uint32_t clues_hi, uint32_t open4_lo, uint32_t open4_hi,
                              uint64_t max_scan, uint64_t chunk, void* d_puzzles, void* d_grids, void* d_level,
                              void* d_open, void* d_open4, void* d_index, uint64_t* found, uint64_t* scanned) {
-    if (!c || !found || (n && (!d_puzzles || !d_grids))) return fail(SDK_EINVAL, "NULL argument");
-    int rc;
-    if ((rc = check_graded_args(first, n, level_mask, clues_lo, clues_hi, max_scan, chunk)) ||
-        (rc = check_subsets_range(open4_lo, open4_hi)))
-        return rc;
-    if ((reinterpret_cast<uintptr_t>(d_puzzles) | reinterpret_cast<uintptr_t>(d_grids)) & 15u)
-        return fail(SDK_EINVAL, "device boards must be 16-byte aligned");
-    if (reinterpret_cast<uintptr_t>(d_index) & 7u) return fail(SDK_EINVAL, "d_index must be 8-byte aligned");
-    uint64_t f = 0, s = 0;
-    if (n) {
-        std::lock_guard<std::mutex> lk(c->mu);
-        HIPCALL(hipSetDevice(c->device));
-        GradedCall g{seed, first, (uint32_t)n, level_mask, clues_lo, clues_hi, max_scan, chunk,
-                     static_cast<uint8_t*>(d_puzzles), static_cast<uint8_t*>(d_grids), static_cast<uint8_t*>(d_level),
-                     static_cast<uint8_t*>(d_open), static_cast<uint64_t*>(d_index)};
-        g.subsets = true;
-        g.o4_lo = open4_lo;
-        g.o4_hi = open4_hi;
-        g.open4 = static_cast<uint8_t*>(d_open4);
-        if ((rc = launch_generate_graded(c, g, &f, &s))) return rc;
-    }
-    *found = f;
-    if (scanned) *scanned = s;
-    return SDK_OK;
+    return graded_call(c, false, n,
+                       subsets_args(graded_args(seed, first, level_mask, clues_lo, clues_hi, max_scan, chunk,
+                                                d_puzzles, d_grids, d_level, d_open, d_index),
+                                    open4_lo, open4_hi, d_open4),
+                       found, scanned);
 }
 
 int sdk_generate_subsets(sdk_ctx* c, uint64_t seed, uint64_t first, size_t n, uint32_t level_mask, uint32_t clues_lo,
                          uint32_t clues_hi, uint32_t open4_lo, uint32_t open4_hi, uint64_t max_scan, uint64_t chunk,
                          uint8_t* puzzles, uint8_t* grids, uint8_t* level, uint8_t* open, uint8_t* open4,
                          uint64_t* index, uint64_t* found, uint64_t* scanned) {
-    if (!c || !found || (n && (!puzzles || !grids))) return fail(SDK_EINVAL, "NULL argument");
-    int rc;
-    if ((rc = check_graded_args(first, n, level_mask, clues_lo, clues_hi, max_scan, chunk)) ||
-        (rc = check_subsets_range(open4_lo, open4_hi)))
-        return rc;
-    uint64_t f = 0, s = 0;
-    if (n) {
-        std::lock_guard<std::mutex> lk(c->mu);
-        HIPCALL(hipSetDevice(c->device));
-        const size_t rows = (size_t)std::min<uint64_t>(n, max_scan);
-        if ((rc = ensure(c->gg_out_puz, rows * 81)) || (rc = ensure(c->gg_out_grid, rows * 81)) ||
-            (level && (rc = ensure(c->gg_out_level, rows))) || (open && (rc = ensure(c->gg_out_open, rows))) ||
-            (open4 && (rc = ensure(c->gg_out_o4, rows))) || (index && (rc = ensure(c->gg_out_index, rows * 8))))
-            return rc;
-        GradedCall g{seed, first, (uint32_t)n, level_mask, clues_lo, clues_hi, max_scan, chunk,
-                     static_cast<uint8_t*>(c->gg_out_puz.p), static_cast<uint8_t*>(c->gg_out_grid.p),
-                     level ? static_cast<uint8_t*>(c->gg_out_level.p) : nullptr,
-                     open ? static_cast<uint8_t*>(c->gg_out_open.p) : nullptr,
-                     index ? static_cast<uint64_t*>(c->gg_out_index.p) : nullptr};
-        g.subsets = true;
-        g.o4_lo = open4_lo;
-        g.o4_hi = open4_hi;
-        g.open4 = open4 ? static_cast<uint8_t*>(c->gg_out_o4.p) : nullptr;
-        if ((rc = launch_generate_graded(c, g, &f, &s))) return rc;
-        if (f) {
-            Staging io(c, {{index ? f * 8 : 0, nullptr, nullptr, g.index, index},
-                           {f * 81, nullptr, nullptr, g.puzzles, puzzles},
-                           {f * 81, nullptr, nullptr, g.grids, grids},
-                           {level ? f : 0, nullptr, nullptr, g.level, level},
-                           {open ? f : 0, nullptr, nullptr, g.open, open},
-                           {open4 ? f : 0, nullptr, nullptr, g.open4, open4}});
-            if ((rc = io.fetch())) return rc;
-        }
-    }
-    *found = f;
-    if (scanned) *scanned = s;
-    return SDK_OK;
+    return graded_call(c, true, n,
+                       subsets_args(graded_args(seed, first, level_mask, clues_lo, clues_hi, max_scan, chunk, puzzles,
+                                                grids, level, open, index),
+                                    open4_lo, open4_hi, open4),
+                       found, scanned);
 }
 
 int sdk_select_rows_dev(sdk_ctx* c, const sdk_select_rows* a, uint64_t* total, uint64_t* last) {

@@ -474,8 +474,9 @@ class SudokuEngine:
         return puzzles, grids, status
 
     @staticmethod
-    def _graded_args(n, levels, seed, lo, clues, max_scan, chunk):
-        """The arguments of sdk_generate_graded from generate_graded's (ValueError for a bad one)."""
+    def _graded_args(n, levels, seed, lo, clues, max_scan, chunk, band=None):
+        """The arguments of sdk_generate_graded from generate_graded's (ValueError for a bad one); band =
+        (name, range) adds the (lo, hi) of sdk_generate_rated's backdoors or sdk_generate_subsets' open4."""
         n, seed, lo = SudokuEngine._stream_rows(n, seed, lo)
         if n >= 1 << 31:
             raise ValueError("n must be below 2^31")
@@ -493,7 +494,39 @@ class SudokuEngine:
             raise ValueError("max_scan must be >= 1 and lo + max_scan an unsigned 64-bit integer")
         if not 0 <= chunk <= L.SDK_GRADED_CHUNK_MAX:
             raise ValueError("chunk must be 0 (automatic) or 1..2^24")
-        return seed, lo, n, mask, clues_lo, clues_hi, max_scan, chunk
+        if band is None:
+            return seed, lo, n, mask, clues_lo, clues_hi, max_scan, chunk
+        name, rng = band
+        f_lo, f_hi = (0, 64) if rng is None else (int(rng[0]), int(rng[1]))
+        if not 0 <= f_lo <= f_hi <= 64:
+            raise ValueError(f"{name} must be (lo, hi) with 0 <= lo <= hi <= 64")
+        return seed, lo, n, mask, clues_lo, clues_hi, f_lo, f_hi, max_scan, chunk
+
+    def _generate_selected(self, family, args, extra):
+        """sdk_generate_<family> on host arrays of min(n, max_scan) rows, `extra` uint8 columns after
+        level and open: (puzzles, solutions, level, open, *extra, index, scanned), `found` rows each."""
+        n, max_scan = args[2], args[-2]     # _graded_args: (seed, lo, n, mask, ..., max_scan, chunk) with or without a band
+        assert len(args) in (8, 10)
+        rows = min(n, max_scan)
+        puzzles = np.empty((rows, 81), dtype=np.uint8)
+        grids = np.empty((rows, 81), dtype=np.uint8)
+        cols = [np.empty(rows, dtype=np.uint8) for _ in range(2 + extra)]
+        index = np.empty(rows, dtype=np.uint64)
+        found, scanned = ctypes.c_uint64(), ctypes.c_uint64()
+        name = "sdk_generate_" + family
+        L.check(getattr(self.lib, name)(self.ctx, *args, _ptr(puzzles), _ptr(grids), *map(_ptr, cols), _ptr(index),
+                                        ctypes.byref(found), ctypes.byref(scanned)), name)
+        f = found.value
+        return (puzzles[:f], grids[:f], *(c[:f] for c in cols), index[:f], scanned.value)
+
+    def _generate_selected_dev(self, family, args, d_puzzles, d_grids, d_cols, d_index):
+        """sdk_generate_<family>_dev; d_cols: the optional device columns between d_grids and d_index."""
+        found, scanned = ctypes.c_uint64(), ctypes.c_uint64()
+        name = "sdk_generate_" + family + "_dev"
+        L.check(getattr(self.lib, name)(self.ctx, *args, d_puzzles.ptr, d_grids.ptr,
+                                        *(b.ptr if b else None for b in d_cols), d_index.ptr if d_index else None,
+                                        ctypes.byref(found), ctypes.byref(scanned)), name)
+        return found.value, scanned.value
 
     def generate_graded(self, n, levels=(1, 2, 3, 4), seed=synth.DEFAULT_SEED + 3, lo=0, clues=None,
                         max_scan=1 << 26, chunk=0):
@@ -505,29 +538,7 @@ class SudokuEngine:
         number of rows up to and including the n-th match (max_scan if there were fewer).  chunk is the
         number of rows per round (0 = automatic): it changes speed and memory only, never the result.
         A bad argument raises ValueError before any launch."""
-        args = self._graded_args(n, levels, seed, lo, clues, max_scan, chunk)
-        rows = min(args[2], args[6])
-        puzzles = np.empty((rows, 81), dtype=np.uint8)
-        grids = np.empty((rows, 81), dtype=np.uint8)
-        level = np.empty(rows, dtype=np.uint8)
-        open_ = np.empty(rows, dtype=np.uint8)
-        index = np.empty(rows, dtype=np.uint64)
-        found, scanned = ctypes.c_uint64(), ctypes.c_uint64()
-        L.check(self.lib.sdk_generate_graded(self.ctx, *args, _ptr(puzzles), _ptr(grids), _ptr(level), _ptr(open_),
-                                             _ptr(index), ctypes.byref(found), ctypes.byref(scanned)),
-                "sdk_generate_graded")
-        f = found.value
-        return puzzles[:f], grids[:f], level[:f], open_[:f], index[:f], scanned.value
-
-    @staticmethod
-    def _rated_args(n, levels, seed, lo, clues, backdoors, max_scan, chunk):
-        """The arguments of sdk_generate_rated from generate_rated's (ValueError for a bad one)."""
-        seed, lo, n, mask, clues_lo, clues_hi, max_scan, chunk = SudokuEngine._graded_args(
-            n, levels, seed, lo, clues, max_scan, chunk)
-        bd_lo, bd_hi = (0, 64) if backdoors is None else (int(backdoors[0]), int(backdoors[1]))
-        if not 0 <= bd_lo <= bd_hi <= 64:
-            raise ValueError("backdoors must be (lo, hi) with 0 <= lo <= hi <= 64")
-        return seed, lo, n, mask, clues_lo, clues_hi, bd_lo, bd_hi, max_scan, chunk
+        return self._generate_selected("graded", self._graded_args(n, levels, seed, lo, clues, max_scan, chunk), 0)
 
     def generate_rated(self, n, levels=(1, 2, 3, 4), seed=synth.DEFAULT_SEED + 3, lo=0, clues=None, backdoors=None,
                        max_scan=1 << 26, chunk=0):
@@ -536,29 +547,8 @@ class SudokuEngine:
         are not filtered by it.  Returns generate_graded's tuple with the ratings after open:
         (puzzles, solutions, level, open, backdoors uint8[found], key uint8[found], index, scanned);
         backdoors and key are 0xFF for the puzzles of levels 1..3."""
-        args = self._rated_args(n, levels, seed, lo, clues, backdoors, max_scan, chunk)
-        rows = min(args[2], args[8])
-        puzzles = np.empty((rows, 81), dtype=np.uint8)
-        grids = np.empty((rows, 81), dtype=np.uint8)
-        level, open_, bd, key = (np.empty(rows, dtype=np.uint8) for _ in range(4))
-        index = np.empty(rows, dtype=np.uint64)
-        found, scanned = ctypes.c_uint64(), ctypes.c_uint64()
-        L.check(self.lib.sdk_generate_rated(self.ctx, *args, _ptr(puzzles), _ptr(grids), _ptr(level), _ptr(open_),
-                                            _ptr(bd), _ptr(key), _ptr(index), ctypes.byref(found),
-                                            ctypes.byref(scanned)),
-                "sdk_generate_rated")
-        f = found.value
-        return puzzles[:f], grids[:f], level[:f], open_[:f], bd[:f], key[:f], index[:f], scanned.value
-
-    @staticmethod
-    def _subsets_args(n, levels, seed, lo, clues, open4, max_scan, chunk):
-        """The arguments of sdk_generate_subsets from generate_subsets's (ValueError for a bad one)."""
-        seed, lo, n, mask, clues_lo, clues_hi, max_scan, chunk = SudokuEngine._graded_args(
-            n, levels, seed, lo, clues, max_scan, chunk)
-        o4_lo, o4_hi = (0, 64) if open4 is None else (int(open4[0]), int(open4[1]))
-        if not 0 <= o4_lo <= o4_hi <= 64:
-            raise ValueError("open4 must be (lo, hi) with 0 <= lo <= hi <= 64")
-        return seed, lo, n, mask, clues_lo, clues_hi, o4_lo, o4_hi, max_scan, chunk
+        args = self._graded_args(n, levels, seed, lo, clues, max_scan, chunk, ("backdoors", backdoors))
+        return self._generate_selected("rated", args, 2)
 
     def generate_subsets(self, n, levels=(1, 2, 3, 4), seed=synth.DEFAULT_SEED + 3, lo=0, clues=None, open4=None,
                          max_scan=1 << 26, chunk=0):
@@ -568,18 +558,8 @@ class SudokuEngine:
         generate_graded's tuple with the counts after open: (puzzles, solutions, level, open, open4
         uint8[found], index, scanned); open4 is 0xFF for the puzzles of levels 1..3.  Not sharded by
         MultiDeviceEngine, like generate_graded and generate_rated."""
-        args = self._subsets_args(n, levels, seed, lo, clues, open4, max_scan, chunk)
-        rows = min(args[2], args[8])
-        puzzles = np.empty((rows, 81), dtype=np.uint8)
-        grids = np.empty((rows, 81), dtype=np.uint8)
-        level, open_, o4 = (np.empty(rows, dtype=np.uint8) for _ in range(3))
-        index = np.empty(rows, dtype=np.uint64)
-        found, scanned = ctypes.c_uint64(), ctypes.c_uint64()
-        L.check(self.lib.sdk_generate_subsets(self.ctx, *args, _ptr(puzzles), _ptr(grids), _ptr(level), _ptr(open_),
-                                              _ptr(o4), _ptr(index), ctypes.byref(found), ctypes.byref(scanned)),
-                "sdk_generate_subsets")
-        f = found.value
-        return puzzles[:f], grids[:f], level[:f], open_[:f], o4[:f], index[:f], scanned.value
+        args = self._graded_args(n, levels, seed, lo, clues, max_scan, chunk, ("open4", open4))
+        return self._generate_selected("subsets", args, 1)
 
     def expand(self, boards, masks=None, target=64):
         """Lex-ordered frontier below `boards` (sdk_expand_boards): uint8[k,81], children in the
@@ -814,41 +794,22 @@ class SudokuEngine:
         optional): -> (found, scanned).  Rows from `found` on are left as they were; the rows are valid
         after synchronize()."""
         args = self._graded_args(n, levels, seed, lo, clues, max_scan, chunk)
-        found, scanned = ctypes.c_uint64(), ctypes.c_uint64()
-        L.check(self.lib.sdk_generate_graded_dev(self.ctx, *args, d_puzzles.ptr, d_grids.ptr,
-                                                 d_level.ptr if d_level else None, d_open.ptr if d_open else None,
-                                                 d_index.ptr if d_index else None, ctypes.byref(found),
-                                                 ctypes.byref(scanned)),
-                "sdk_generate_graded_dev")
-        return found.value, scanned.value
+        return self._generate_selected_dev("graded", args, d_puzzles, d_grids, (d_level, d_open), d_index)
 
     def generate_rated_dev(self, d_puzzles, d_grids, n, levels=(1, 2, 3, 4), seed=synth.DEFAULT_SEED + 3, lo=0,
                            clues=None, backdoors=None, max_scan=1 << 26, chunk=0, d_level=None, d_open=None,
                            d_backdoors=None, d_key=None, d_index=None):
         """generate_rated into device buffers of n rows, as generate_graded_dev: -> (found, scanned)."""
-        args = self._rated_args(n, levels, seed, lo, clues, backdoors, max_scan, chunk)
-        found, scanned = ctypes.c_uint64(), ctypes.c_uint64()
-        L.check(self.lib.sdk_generate_rated_dev(self.ctx, *args, d_puzzles.ptr, d_grids.ptr,
-                                                d_level.ptr if d_level else None, d_open.ptr if d_open else None,
-                                                d_backdoors.ptr if d_backdoors else None,
-                                                d_key.ptr if d_key else None, d_index.ptr if d_index else None,
-                                                ctypes.byref(found), ctypes.byref(scanned)),
-                "sdk_generate_rated_dev")
-        return found.value, scanned.value
+        args = self._graded_args(n, levels, seed, lo, clues, max_scan, chunk, ("backdoors", backdoors))
+        return self._generate_selected_dev("rated", args, d_puzzles, d_grids, (d_level, d_open, d_backdoors, d_key),
+                                           d_index)
 
     def generate_subsets_dev(self, d_puzzles, d_grids, n, levels=(1, 2, 3, 4), seed=synth.DEFAULT_SEED + 3, lo=0,
                              clues=None, open4=None, max_scan=1 << 26, chunk=0, d_level=None, d_open=None,
                              d_open4=None, d_index=None):
         """generate_subsets into device buffers of n rows, as generate_graded_dev: -> (found, scanned)."""
-        args = self._subsets_args(n, levels, seed, lo, clues, open4, max_scan, chunk)
-        found, scanned = ctypes.c_uint64(), ctypes.c_uint64()
-        L.check(self.lib.sdk_generate_subsets_dev(self.ctx, *args, d_puzzles.ptr, d_grids.ptr,
-                                                  d_level.ptr if d_level else None, d_open.ptr if d_open else None,
-                                                  d_open4.ptr if d_open4 else None,
-                                                  d_index.ptr if d_index else None, ctypes.byref(found),
-                                                  ctypes.byref(scanned)),
-                "sdk_generate_subsets_dev")
-        return found.value, scanned.value
+        args = self._graded_args(n, levels, seed, lo, clues, max_scan, chunk, ("open4", open4))
+        return self._generate_selected_dev("subsets", args, d_puzzles, d_grids, (d_level, d_open, d_open4), d_index)
 
     def select_rows_dev(self, rows):
         """One round of the graded selection on caller-supplied device rows (sdk_select_rows_dev): `rows`
