@@ -5,6 +5,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "canon_args.h"
 #include "check_args.h"
 #include "donate_args.h"
 #include "frontier_args.h"
@@ -50,6 +51,9 @@ hipError_t launch_reduce32(const Reduce32Args& a, unsigned grid, hipStream_t str
 
 // subsets_launch.hip: one half-wave per level-4 board of the grade pass's list (its length is on the device)
 hipError_t launch_subsets32(const Subsets32Args& a, unsigned grid, hipStream_t stream);
+
+// canon_launch.hip: one wave per board (grid-stride over the slice)
+hipError_t launch_canon(const CanonArgs& a, unsigned grid, hipStream_t stream);
 
 // select_launch.hip: one wave per tile of 64 rows (flag, scatter), one workgroup (scan)
 hipError_t launch_select_flag(const SelFlagArgs& a, uint32_t tiles, hipStream_t stream);

@@ -194,6 +194,8 @@ struct sdk_ctx {
     DevBuf gg_out_puz, gg_out_grid, gg_out_level, gg_out_open, gg_out_index;
     DevBuf gg_bd, gg_key, gg_out_bd, gg_out_key;   // sdk_generate_rated: a round's ratings, the host call's
     DevBuf s4_open4, gg_o4, gg_out_o4;   // sdk_subsets_batch (host pointers); sdk_generate_subsets: a round's, the host call's
+    DevBuf cn_sol;                 // sdk_canonical_batch_dev without a solution buffer: a slice's completions
+    DevBuf cn_gather, cn_relabel, cn_ties;   // sdk_canonical_batch: the host-pointer call's symmetries and tie counts
     DevBuf fr_a, fr_b, prop, bcell, bmask, nchild, offs, fr_status, fr_mask, tsum, fr_ctl;
     DevBuf fr_tail;                // refine_head: the boards kept after the refined ones
     // the device-resident frontier of the last sdk_frontier_build (in fr_a)
@@ -956,6 +958,48 @@ int launch_grade(sdk_ctx* c, const uint8_t* d_in, uint8_t* d_out, int8_t* d_stat
             if (sdk::launch_subsets32(s, grid_for(c, m, 2, 16), c->stream) != hipSuccess)
                 rc = fail(SDK_EHIP, "subsets launch failed");
         }
+    }
+    return span.end(rc);
+}
+
+// Canonical forms (sdk_canonical_batch; canon_kernel.h): per slice of kDnCapBoards, the classify path
+// (launch_classify: its statuses and completions, under every option and budget) and then one launch of
+// the canonical-form kernel, one wave per board, at most 16 one-wave workgroups per CU (four waves per
+// SIMD).  The completions go to d_solution, or to the context's cn_sol where the caller wants none; the
+// kernel overwrites an eligible board's completion with its canonical solution in place.  d_canon may be
+// d_in: classify has read a slice's boards before the kernel writes them, and a wave reads its board before
+// it writes.  One span under SDK_OPT_TIMING; outcome fields as the classify of the last slice.
+struct CanonCols {
+    uint8_t *solution, *gather, *relabel;
+    uint16_t* ties;
+};
+
+int launch_canonical(sdk_ctx* c, const uint8_t* d_in, uint8_t* d_canon, int8_t* d_status, const CanonCols& cols,
+                     size_t n, int64_t budget) {
+    if (n == 0) return SDK_OK;
+    if ((reinterpret_cast<uintptr_t>(d_in) | reinterpret_cast<uintptr_t>(d_canon)) & 15u)
+        return fail(SDK_EINVAL, "device boards must be 16-byte aligned");
+    const uint64_t cap = std::min<uint64_t>(n, kDnCapBoards);
+    int rc;
+    if (!cols.solution && (rc = ensure(c->cn_sol, cap * 81))) return rc;
+    TimedSpan span(c);
+    if ((rc = span.begin())) return rc;
+    for (uint64_t b0 = 0; b0 < n && !rc; b0 += kDnCapBoards) {
+        const uint64_t m = std::min<uint64_t>(n - b0, kDnCapBoards);
+        uint8_t* sol = cols.solution ? cols.solution + b0 * 81 : static_cast<uint8_t*>(c->cn_sol.p);
+        if ((rc = launch_classify(c, d_in + b0 * 81, sol, d_status + b0, m, budget))) break;
+        sdk::CanonArgs a{};
+        a.in = d_in + b0 * 81;
+        a.sol = sol;
+        a.status = d_status + b0;
+        a.n = m;
+        a.canon = d_canon + b0 * 81;
+        a.solution = cols.solution ? sol : nullptr;
+        a.gather = cols.gather ? cols.gather + b0 * 81 : nullptr;
+        a.relabel = cols.relabel ? cols.relabel + b0 * 10 : nullptr;
+        a.ties = cols.ties ? cols.ties + b0 : nullptr;
+        if (sdk::launch_canon(a, grid_for(c, m, 1, 16), c->stream) != hipSuccess)
+            rc = fail(SDK_EHIP, "canonical-form launch failed");
     }
     return span.end(rc);
 }
@@ -2314,6 +2358,50 @@ int sdk_subsets_batch(sdk_ctx* c, const uint8_t* in, uint8_t* out, int8_t* statu
                       uint8_t* open4, size_t n, uint64_t node_budget) {
     if (!c || (n && (!in || !out || !status || !level || !open4))) return fail(SDK_EINVAL, "NULL argument");
     return grade_call(c, true, in, out, status, {level, open, nullptr, nullptr, open4}, n, node_budget);
+}
+
+int sdk_canonical_batch_dev(sdk_ctx* c, const void* d_in, void* d_canon, void* d_solution, void* d_status,
+                            void* d_gather, void* d_relabel, void* d_ties, size_t n, uint64_t node_budget) {
+    if (!c || (n && (!d_in || !d_canon || !d_status))) return fail(SDK_EINVAL, "NULL argument");
+    int rc;
+    if ((rc = check_budget_arg(node_budget))) return rc;
+    if (n == 0) return SDK_OK;
+    if ((rc = check_board_count(n))) return rc;
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCALL(hipSetDevice(c->device));
+    return launch_canonical(c, static_cast<const uint8_t*>(d_in), u8(d_canon), static_cast<int8_t*>(d_status),
+                            {u8(d_solution), u8(d_gather), u8(d_relabel), static_cast<uint16_t*>(d_ties)}, n,
+                            budget_arg(node_budget));
+}
+
+int sdk_canonical_batch(sdk_ctx* c, const uint8_t* in, uint8_t* canon, uint8_t* solution, int8_t* status,
+                        uint8_t* gather, uint8_t* relabel, uint16_t* ties, size_t n, uint64_t node_budget) {
+    if (!c || (n && (!in || !canon || !status))) return fail(SDK_EINVAL, "NULL argument");
+    int rc;
+    if ((rc = check_budget_arg(node_budget))) return rc;
+    if (n == 0) return SDK_OK;
+    if ((rc = check_board_count(n))) return rc;
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCALL(hipSetDevice(c->device));
+    // the boards are canonised in place in c->in; the completions always go through c->out
+    if ((rc = ensure(c->in, n * 81)) || (rc = ensure(c->out, n * 81)) || (rc = ensure(c->status, n)) ||
+        (gather && (rc = ensure(c->cn_gather, n * 81))) || (relabel && (rc = ensure(c->cn_relabel, n * 10))) ||
+        (ties && (rc = ensure(c->cn_ties, n * 2))))
+        return rc;
+    uint8_t* d_in = u8(c->in.p);
+    int8_t* d_status = static_cast<int8_t*>(c->status.p);
+    const CanonCols d{u8(c->out.p), gather ? u8(c->cn_gather.p) : nullptr, relabel ? u8(c->cn_relabel.p) : nullptr,
+                      ties ? static_cast<uint16_t*>(c->cn_ties.p) : nullptr};
+    // a nullable output comes back iff the caller has it (a slot each, present or not)
+    auto back = [](size_t bytes, const void* dev, void* dst) { return Piece{dst ? bytes : 0, nullptr, nullptr, dev, dst}; };
+    Staging io(c, {back(n * 2, d.ties, ties),
+                   {n * 81, in, d_in, d_in, canon},
+                   back(n * 81, d.solution, solution),
+                   back(n * 81, d.gather, gather),
+                   back(n * 10, d.relabel, relabel),
+                   {n, nullptr, nullptr, d_status, status}});
+    if ((rc = io.send()) || (rc = launch_canonical(c, d_in, d_in, d_status, d, n, budget_arg(node_budget)))) return rc;
+    return io.fetch();
 }
 
 int sdk_minimize_batch_dev(sdk_ctx* c, const void* d_in, const void* d_order, void* d_out, void* d_status, size_t n) {

@@ -364,6 +364,31 @@ class SudokuEngine:
                 "sdk_subsets_batch")
         return status, level, open_, open4, out
 
+    def canonical_batch(self, boards, budget=None):
+        """uint8[n,81] -> (status int8[n], canon uint8[n,81], solution uint8[n,81], gather uint8[n,81],
+        relabel uint8[n,10], ties uint16[n]): the canonical form of each board under the Sudoku
+        symmetries (sdk_canonical_batch).  status is classify_batch's.  For a board with exactly one
+        completion and clean givens, canon is the smallest image of the board among the symmetries that
+        take its completion to the smallest image of any, solution is that image of the completion,
+        (gather, relabel) is the symmetry in synth.apply_symmetries' form and ties the number of
+        automorphisms of the completion.  Two such boards are the same puzzle iff their canon rows are
+        equal: np.unique(canon[status == 1], axis=0) dedupes a corpus.  Every other board comes back
+        unchanged with the identity symmetry, ties 0 and classify_batch's out as solution.  Like
+        grade_batch this call is not sharded by MultiDeviceEngine or ShardedBatch."""
+        boards = np.ascontiguousarray(boards, dtype=np.uint8).reshape(-1, 81)
+        n = boards.shape[0]
+        if budget is not None and not 0 <= int(budget) < (1 << 63):
+            raise ValueError("budget must be 0 (unlimited) or a positive node count")
+        canon, solution, gather = (np.empty_like(boards) for _ in range(3))
+        status = np.empty(n, dtype=np.int8)
+        relabel = np.empty((n, 10), dtype=np.uint8)
+        ties = np.empty(n, dtype=np.uint16)
+        L.check(self.lib.sdk_canonical_batch(self.ctx, _ptr(boards), _ptr(canon), _ptr(solution), _ptr(status),
+                                             _ptr(gather), _ptr(relabel), _ptr(ties), n,
+                                             L.SDK_BUDGET_CONTEXT if budget is None else int(budget)),
+                "sdk_canonical_batch")
+        return status, canon, solution, gather, relabel, ties
+
     @staticmethod
     def check_order(order, n):
         """order -> uint8[n,81], every row a permutation of 0..80 (else ValueError)."""
@@ -759,6 +784,16 @@ class SudokuEngine:
                                                d_open.ptr if d_open else None, d_open4.ptr, int(n),
                                                L.SDK_BUDGET_CONTEXT if budget is None else int(budget)),
                 "sdk_subsets_batch_dev")
+
+    def canonical_batch_dev(self, d_in, d_canon, d_status, n, d_solution=None, d_gather=None, d_relabel=None,
+                            d_ties=None, budget=None):
+        """canonical_batch on device buffers: d_in and d_canon 16-byte aligned (d_canon may be d_in);
+        d_solution, d_gather, d_relabel (10 bytes per board) and d_ties (uint16 per board) optional."""
+        opt = lambda d: d.ptr if d else None
+        L.check(self.lib.sdk_canonical_batch_dev(self.ctx, d_in.ptr, d_canon.ptr, opt(d_solution), d_status.ptr,
+                                                 opt(d_gather), opt(d_relabel), opt(d_ties), int(n),
+                                                 L.SDK_BUDGET_CONTEXT if budget is None else int(budget)),
+                "sdk_canonical_batch_dev")
 
     def minimize_batch_dev(self, d_in, d_order, d_out, d_status, n):
         """The order rows are not validated on this path (see include/sudoku_hip.h)."""

@@ -12,6 +12,8 @@
  *       -> sdk_solve_batch / sdk_solve_batch_dev
  *   Sudoku(grid).check() -> bool            sudoku.py:43-94
  *       -> sdk_check_batch / sdk_check_batch_dev
+ *   (no reference counterpart: is this board that board under the Sudoku symmetries?)
+ *       -> sdk_canonical_batch
  *   (no reference counterpart)
  *       -> sdk_count_solutions
  *   (no reference counterpart: a batch's verdicts, the technique a board needs,
@@ -55,6 +57,7 @@ extern "C" {
                             /* and sdk_subsets_batch[_dev] and sdk_generate_subsets[_dev]         */
                             /* and sdk_minimize_level_batch[_dev], sdk_generate_level[_dev]       */
                             /* and sdk_select_rows_dev                                            */
+                            /* and sdk_canonical_batch[_dev]                                      */
                             /* (new symbols only: nothing a version-2 caller uses changed)        */
 
 /* return codes */
@@ -336,6 +339,50 @@ int sdk_rate_batch(sdk_ctx *ctx, const uint8_t *in, uint8_t *out, int8_t *status
 #define SDK_SUBSETS_NONE 0xFFu
 int sdk_subsets_batch(sdk_ctx *ctx, const uint8_t *in, uint8_t *out, int8_t *status, uint8_t *level,
                       uint8_t *open, uint8_t *open4, size_t n, uint64_t node_budget);
+
+/* Canonical forms for n boards: are two boards the same puzzle under the Sudoku symmetries?
+ *
+ * A symmetry is a pair (g, rho).  g is a permutation of the cells 0..80 (new cell -> old cell) made of a
+ * row permutation and a column permutation that keep bands and stacks, and optionally the transposition:
+ * 2 * 6^8 = 3,359,232 cell maps.  rho is a permutation of 1..9 with rho[0] = 0.
+ * image(B)[c] = rho[B[g[c]]].
+ *
+ * A board is eligible when sdk_classify_batch gives it SDK_SOLVED and its givens are clean, as
+ * sdk_grade_batch defines clean -- equivalently its completion S is a valid grid (a completion keeps a
+ * duplicated or inert given).  For an eligible board P with completion S:
+ *   M     the canonical solution: the lexicographically smallest image(S) over all symmetries, 81 bytes
+ *         row-major.  Its first row is 1..9.
+ *   C     the canonical puzzle: the lexicographically smallest image(P), 0 = empty sorting first, over the
+ *         symmetries with image(S) == M.  Two eligible boards are equivalent iff their C are equal: the
+ *         symmetries that take S' = T(S) to M are those that take S to M composed with the inverse of T,
+ *         so both boards minimise over the same set of images.
+ *   ties  the number of cell maps g for which some rho gives image(S) == M: the order of the
+ *         automorphism group of S, 1 for almost every grid, at most 648.
+ *   the returned symmetry: among those that attain C, the one of lowest candidate index
+ *         k = (t * 9 + r0) * 1296 + q.  t = 1: G is the transpose of S, else G = S; r0 is the row of G
+ *         that becomes row 0; q = ((s * 6 + i0) * 6 + i1) * 6 + i2 arranges the columns over the six
+ *         permutations P3 = 012, 021, 102, 120, 201, 210: image column j is column
+ *         3 * P3[s][j / 3] + P3[i_(j / 3)][j % 3] of G.  With image rows rr and columns cc of G,
+ *         g[9 i + j] = 9 * rr[i] + cc[j] for t = 0 and 9 * cc[j] + rr[i] for t = 1.
+ * The result is a pure function of the board, and the canonical form of C is C under the identity.
+ *
+ * The reduction behind the candidates: given (t, r0, q), rho is forced by "row 0 of the image is 1..9", and
+ * the rest of the minimal image by sorting -- the rows of a band differ in column 0, so row 0's band-mates
+ * follow in ascending order of their relabelled first cell, each other band is sorted the same way, and
+ * the band that holds the smaller first cell comes first.  M is the minimum over 2 * 9 * 1296 = 23,328
+ * candidates, and every symmetry with image M is exactly one of them.
+ *
+ *   canon     uint8[n][81], required: C; the input for an ineligible board.
+ *   status    required: exactly sdk_classify_batch's, under every option and budget (node_budget as there).
+ *   solution  uint8[n][81], nullable: M for an eligible board, classify's `out` for every other.
+ *   gather    uint8[n][81], nullable: g;  relabel  uint8[n][10], nullable: rho;  ties  uint16[n], nullable.
+ *             An ineligible board (no or several completions, budget hit, unclean givens) has the identity
+ *             gather 0..80, the identity relabel 0..9 and ties 0.
+ * The classify path, then one launch of canon_kernel.h per slice (one board per wave).  It changes no
+ * option and leaves SDK_OPT_PROP32_UNDECIDED as a classify call does.  Any n up to 2^31-1 (slices of 2^24
+ * boards); one span under SDK_OPT_TIMING. */
+int sdk_canonical_batch(sdk_ctx *ctx, const uint8_t *in, uint8_t *canon, uint8_t *solution, int8_t *status,
+                        uint8_t *gather, uint8_t *relabel, uint16_t *ties, size_t n, uint64_t node_budget);
 
 /* Greedy clue removal for n boards.  order is uint8[n][81]; row i is a permutation of 0..80, the
  * cell order in which board i's clues are tried (anything else: SDK_EINVAL).  Per board:
@@ -646,6 +693,11 @@ int sdk_rate_batch_dev(sdk_ctx *ctx, const void *d_in, void *d_out, void *d_stat
  * or NULL. */
 int sdk_subsets_batch_dev(sdk_ctx *ctx, const void *d_in, void *d_out, void *d_status, void *d_level,
                           void *d_open, void *d_open4, size_t n, uint64_t node_budget);
+/* d_in and d_canon 16-byte aligned, else SDK_EINVAL; d_canon may be d_in (exactly).  d_solution, d_gather,
+ * d_relabel and d_ties (uint16[n]) or NULL; a d_solution that is not 16-byte aligned only skips the
+ * propagation pass, as in sdk_classify_batch_dev. */
+int sdk_canonical_batch_dev(sdk_ctx *ctx, const void *d_in, void *d_canon, void *d_solution, void *d_status,
+                            void *d_gather, void *d_relabel, void *d_ties, size_t n, uint64_t node_budget);
 /* d_grids (and d_order, d_puzzles) 16-byte aligned, else SDK_EINVAL; d_order and d_placements
  * (uint32[n]) nullable.  Spans as the host-pointer forms: one per call. */
 int sdk_generate_grids_dev(sdk_ctx *ctx, uint64_t seed, uint64_t first, size_t n, void *d_grids,
