@@ -37,6 +37,8 @@ SDK_GRADED_CHUNK_MAX = 1 << 24
 SDK_RATE_NONE = 0xFF
 # sdk_subsets_batch: open4 of a board that is not of level SDK_GRADE_SEARCH
 SDK_SUBSETS_NONE = 0xFF
+# sdk_fish_batch: open5 of a board that is not of level SDK_GRADE_SEARCH
+SDK_FISH_NONE = 0xFF
 
 SDK_CHECK_OK = 1
 SDK_CHECK_RAW_NAMEERROR = 2
@@ -142,6 +144,8 @@ SIGNATURES = {
     "sdk_rate_batch_dev": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, ctypes.c_uint64]),
     "sdk_subsets_batch": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, ctypes.c_uint64]),
     "sdk_subsets_batch_dev": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, ctypes.c_uint64]),
+    "sdk_fish_batch": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, ctypes.c_uint64]),
+    "sdk_fish_batch_dev": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, ctypes.c_uint64]),
     # (ctx, in, canon, solution, status, gather, relabel, ties, n, node_budget)
     "sdk_canonical_batch": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, ctypes.c_uint64]),
     "sdk_canonical_batch_dev": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, ctypes.c_uint64]),
@@ -180,6 +184,12 @@ SIGNATURES = {
                                                 ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
                                                 ctypes.c_uint64, ctypes.c_uint64, _vp, _vp, _vp, _vp, _vp, _vp,
                                                 ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]),
+    "sdk_generate_fish": (ctypes.c_int, [_vp, ctypes.c_uint64, ctypes.c_uint64, _sz] + [ctypes.c_uint32] * 7 +
+                          [ctypes.c_uint64, ctypes.c_uint64] + [_vp] * 7 +
+                          [ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]),
+    "sdk_generate_fish_dev": (ctypes.c_int, [_vp, ctypes.c_uint64, ctypes.c_uint64, _sz] + [ctypes.c_uint32] * 7 +
+                              [ctypes.c_uint64, ctypes.c_uint64] + [_vp] * 7 +
+                              [ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]),
     "sdk_select_rows_dev": (ctypes.c_int, [_vp, ctypes.POINTER(SelectRows), ctypes.POINTER(ctypes.c_uint64),
                                            ctypes.POINTER(ctypes.c_uint64)]),
     "sdk_frontier_boards_dev": (ctypes.c_int, [_vp, ctypes.POINTER(_vp), ctypes.POINTER(ctypes.c_uint64)]),

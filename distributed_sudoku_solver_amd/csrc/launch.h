@@ -8,6 +8,7 @@
 #include "canon_args.h"
 #include "check_args.h"
 #include "donate_args.h"
+#include "fish_args.h"
 #include "frontier_args.h"
 #include "generate_args.h"
 #include "minimize_args.h"
@@ -51,6 +52,9 @@ hipError_t launch_reduce32(const Reduce32Args& a, unsigned grid, hipStream_t str
 
 // subsets_launch.hip: one half-wave per level-4 board of the grade pass's list (its length is on the device)
 hipError_t launch_subsets32(const Subsets32Args& a, unsigned grid, hipStream_t stream);
+
+// fish_launch.hip: the same work items and layout, with the fish rounds and both counts
+hipError_t launch_fish32(const Fish32Args& a, unsigned grid, hipStream_t stream);
 
 // canon_launch.hip: one wave per board (grid-stride over the slice)
 hipError_t launch_canon(const CanonArgs& a, unsigned grid, hipStream_t stream);

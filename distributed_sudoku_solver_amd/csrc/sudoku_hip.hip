@@ -194,6 +194,8 @@ struct sdk_ctx {
     DevBuf gg_out_puz, gg_out_grid, gg_out_level, gg_out_open, gg_out_index;
     DevBuf gg_bd, gg_key, gg_out_bd, gg_out_key;   // sdk_generate_rated: a round's ratings, the host call's
     DevBuf s4_open4, gg_o4, gg_out_o4;   // sdk_subsets_batch (host pointers); sdk_generate_subsets: a round's, the host call's
+    DevBuf f5_open5, gg_o5, gg_out_o5;   // sdk_fish_batch, sdk_generate_fish: the same for open5 (open4 goes through the above)
+    DevBuf f5_open4;                     // the fish stage's open4 of a slice where the caller wants none
     DevBuf cn_sol;                 // sdk_canonical_batch_dev without a solution buffer: a slice's completions
     DevBuf cn_gather, cn_relabel, cn_ties;   // sdk_canonical_batch: the host-pointer call's symmetries and tie counts
     DevBuf fr_a, fr_b, prop, bcell, bmask, nchild, offs, fr_status, fr_mask, tsum, fr_ctl;
@@ -312,14 +314,14 @@ struct Piece {
 };
 
 // The copies of a host-pointer call: send() before the launch, fetch() after it (it synchronizes).
-// The (at most eight) pieces lie in the pinned area (HostBuf) in the order given -- widest element
+// The (at most nine: sdk_generate_fish) pieces lie in the pinned area (HostBuf) in the order given -- widest element
 // type first, so every slot is aligned for its type; a call too large for the area copies straight
 // from / to the caller's pageable memory.  An error return between send() and the end of fetch()
 // may leave copies from / into the area queued, so the stream is drained first: the next call's
 // memcpy into the area (or a grow that frees it) cannot race them.
 class Staging {
     sdk_ctx* c;
-    Piece p[8];
+    Piece p[9];
     int np = 0;
     bool armed = true;
 
@@ -880,18 +882,23 @@ int launch_classify(sdk_ctx* c, const uint8_t* d_in, uint8_t* d_out, int8_t* d_s
 // the same work items -- the slice's counts filled with SDK_SUBSETS_NONE, the same counter cleared, one
 // half-wave per level-4 board of the list.  It reads the parents only.  Without the pointer nothing of
 // it is enqueued.
+// d_open5 non-null (sdk_fish_batch; fish_kernel.h): the fish stage, where the subsets stage sits and in
+// place of it -- it computes both counts.  Both columns filled with 0xFF, the same counter cleared, the
+// same grid (one half-wave per level-4 board of the list, four waves per SIMD).  d_open4 null: the slice's
+// open4 goes to the context's f5_open4.  Without the pointer nothing of it is enqueued.
 // The columns of a grade call beside out and status, one byte per board: level always, the others nullable.
 struct GradeCols {
     uint8_t *level, *open;
     uint8_t *backdoors, *key;   // the rate stage (sdk_rate_batch)
     uint8_t* open4;             // the subsets stage (sdk_subsets_batch)
+    uint8_t* open5 = nullptr;   // the fish stage (sdk_fish_batch), which fills open4 too
 };
 
 int launch_grade(sdk_ctx* c, const uint8_t* d_in, uint8_t* d_out, int8_t* d_status, const GradeCols& cols, size_t n,
                  int64_t budget) {
     if (n == 0) return SDK_OK;
     uint8_t *const d_level = cols.level, *const d_open = cols.open, *const d_bd = cols.backdoors,
-                   *const d_key = cols.key, *const d_open4 = cols.open4;
+                   *const d_key = cols.key, *const d_open4 = cols.open4, *const d_open5 = cols.open5;
     if ((reinterpret_cast<uintptr_t>(d_in) | reinterpret_cast<uintptr_t>(d_out)) & 15u)
         return fail(SDK_EINVAL, "device boards must be 16-byte aligned");
     if (budget < 0) budget = (int64_t)c->budget;
@@ -899,7 +906,7 @@ int launch_grade(sdk_ctx* c, const uint8_t* d_in, uint8_t* d_out, int8_t* d_stat
     const bool in_place = d_in == d_out;
     int rc;
     if ((rc = p32_reserve(c, cap)) || (in_place && (rc = ensure(c->gr_in, cap * 81))) ||
-        (!d_open && (rc = ensure(c->gr_open, cap))))
+        (!d_open && (rc = ensure(c->gr_open, cap))) || (d_open5 && !d_open4 && (rc = ensure(c->f5_open4, cap))))
         return rc;
     TimedSpan span(c);
     if ((rc = span.begin())) return rc;
@@ -944,7 +951,22 @@ int launch_grade(sdk_ctx* c, const uint8_t* d_in, uint8_t* d_out, int8_t* d_stat
             if (sdk::launch_rate32(r, grid_for(c, m, 1, 16), c->stream) != hipSuccess)
                 rc = fail(SDK_EHIP, "rate launch failed");
         }
-        if (!rc && d_open4) {
+        if (!rc && d_open5) {
+            sdk::Fish32Args f{};
+            f.in = in;
+            f.level = a.level;
+            f.list = a.p.list;
+            f.n = m;
+            f.next = a.p.heads;
+            f.open4 = d_open4 ? d_open4 + b0 : static_cast<uint8_t*>(c->f5_open4.p);
+            f.open5 = d_open5 + b0;
+            HIPCALL(hipMemsetAsync(f.open4, 0xFF, m, c->stream));
+            HIPCALL(hipMemsetAsync(f.open5, 0xFF, m, c->stream));
+            HIPCALL(hipMemsetAsync(f.next, 0, 4, c->stream));
+            // four waves per SIMD; at most one wave per two listed boards
+            if (sdk::launch_fish32(f, grid_for(c, m, 2, 16), c->stream) != hipSuccess)
+                rc = fail(SDK_EHIP, "fish launch failed");
+        } else if (!rc && d_open4) {
             sdk::Subsets32Args s{};
             s.in = in;
             s.level = a.level;
@@ -1198,6 +1220,10 @@ struct GradedCall {
     bool subsets = false;
     uint32_t o4_lo = 0, o4_hi = 64;
     uint8_t* open4 = nullptr;
+    // sdk_generate_fish: both o4_lo <= open4 <= o4_hi and o5_lo <= open5 <= o5_hi, and the fish stage
+    bool fish = false;
+    uint32_t o5_lo = 0, o5_hi = 64;
+    uint8_t* open5 = nullptr;
 };
 
 // One round's selection (select_kernel.h): rows [0, m) of caller-supplied buffers -- a round of
@@ -1317,9 +1343,11 @@ int launch_generate_graded(sdk_ctx* c, const GradedCall& g, uint64_t* found, uin
         if (rate && ((rc = ensure(c->gg_bd, rows)) || (rc = ensure(c->gg_key, rows)))) return rc;
         uint8_t* bd = rate ? static_cast<uint8_t*>(c->gg_bd.p) : nullptr;
         uint8_t* key = rate ? static_cast<uint8_t*>(c->gg_key.p) : nullptr;
-        const bool subsets = g.subsets && (g.level_mask >> SDK_GRADE_SEARCH & 1u);
-        if (subsets && (rc = ensure(c->gg_o4, rows))) return rc;
+        const bool fish = g.fish && (g.level_mask >> SDK_GRADE_SEARCH & 1u);
+        const bool subsets = fish || (g.subsets && (g.level_mask >> SDK_GRADE_SEARCH & 1u));
+        if ((subsets && (rc = ensure(c->gg_o4, rows))) || (fish && (rc = ensure(c->gg_o5, rows)))) return rc;
         uint8_t* o4 = subsets ? static_cast<uint8_t*>(c->gg_o4.p) : nullptr;
+        uint8_t* o5 = fish ? static_cast<uint8_t*>(c->gg_o5.p) : nullptr;
         uint8_t* puz = static_cast<uint8_t*>(c->gg_puz.p);
         uint8_t* grid = static_cast<uint8_t*>(c->gg_grid.p);
         int8_t* st = static_cast<int8_t*>(c->gg_st.p);
@@ -1327,7 +1355,7 @@ int launch_generate_graded(sdk_ctx* c, const GradedCall& g, uint64_t* found, uin
         uint8_t* open = static_cast<uint8_t*>(c->gg_open.p);
         if ((rc = launch_generate_puzzles(c, g.seed, g.first + done, m, puz, grid, st)) ||
             (rc = launch_grade(c, puz, static_cast<uint8_t*>(c->gg_sol.p), static_cast<int8_t*>(c->gg_gst.p),
-                               GradeCols{level, open, bd, key, o4}, m, 0)))
+                               GradeCols{level, open, bd, key, o4, o5}, m, 0)))
             return rc;
         SelectRound r{};
         r.puzzles = puz;
@@ -1356,6 +1384,15 @@ int launch_generate_graded(sdk_ctx* c, const GradedCall& g, uint64_t* found, uin
         r.out_backdoors = g.backdoors;
         r.out_key = g.key;
         r.out_open4 = g.open4;
+        if (g.fish) {
+            // The selection kernels carry two nullable rating columns with a range each, and both "none"
+            // markers are 0xFF: a fish call's open5 column and range go through the `backdoors` slot with
+            // `key` null (a fish call is never rated), its open4 through the `open4` slot as above.
+            r.backdoors = o5;
+            r.bd_lo = g.o5_lo;
+            r.bd_hi = g.o5_hi;
+            r.out_backdoors = g.open5;
+        }
         if ((rc = launch_select_round(c, r, d_word))) return rc;
         sdk::SelWord word;
         HIPCALL(hipMemcpyAsync(&word, d_word, sizeof word, hipMemcpyDeviceToHost, c->stream));
@@ -1399,9 +1436,15 @@ int check_subsets_range(uint32_t lo, uint32_t hi) {
     return SDK_OK;
 }
 
+// ... and the open5 range of sdk_generate_fish
+int check_fish_range(uint32_t lo, uint32_t hi) {
+    if (lo > hi || hi > 64) return fail(SDK_EINVAL, "open5 range must be open5_lo <= open5_hi <= 64");
+    return SDK_OK;
+}
+
 uint8_t* u8(void* p) { return static_cast<uint8_t*>(p); }
 
-// sdk_grade_batch, sdk_rate_batch, sdk_subsets_batch and their _dev forms, behind each one's own test of
+// sdk_grade_batch, sdk_rate_batch, sdk_subsets_batch, sdk_fish_batch and their _dev forms, behind each one's own test of
 // its required pointers: `cols` holds the columns the entry point has, the others null.  host: the pointers
 // are the caller's arrays, staged through the context's buffers (the same ones whichever family calls);
 // else they are device pointers and the call only enqueues.
@@ -1419,14 +1462,14 @@ int grade_call(sdk_ctx* c, bool host, const void* in, void* out, void* status, c
     if ((rc = ensure(c->in, n * 81)) || (rc = ensure(c->out, n * 81)) || (rc = ensure(c->status, n)) ||
         (rc = ensure(c->gr_level, n)) || (cols.open && (rc = ensure(c->gr_open, n))) ||
         (cols.backdoors && (rc = ensure(c->rt_bd, n))) || (cols.key && (rc = ensure(c->rt_key, n))) ||
-        (cols.open4 && (rc = ensure(c->s4_open4, n))))
+        (cols.open4 && (rc = ensure(c->s4_open4, n))) || (cols.open5 && (rc = ensure(c->f5_open5, n))))
         return rc;
     uint8_t* d_in = u8(c->in.p);
     uint8_t* d_out = u8(c->out.p);
     int8_t* d_status = static_cast<int8_t*>(c->status.p);
     const GradeCols d{u8(c->gr_level.p), cols.open ? u8(c->gr_open.p) : nullptr,
                       cols.backdoors ? u8(c->rt_bd.p) : nullptr, cols.key ? u8(c->rt_key.p) : nullptr,
-                      cols.open4 ? u8(c->s4_open4.p) : nullptr};
+                      cols.open4 ? u8(c->s4_open4.p) : nullptr, cols.open5 ? u8(c->f5_open5.p) : nullptr};
     // a column comes back iff the caller has it (a slot each, present or not)
     auto column = [n](const uint8_t* dev, uint8_t* dst) { return Piece{dst ? n : 0, nullptr, nullptr, dev, dst}; };
     Staging io(c, {{n * 81, in, d_in, d_out, out},
@@ -1435,12 +1478,13 @@ int grade_call(sdk_ctx* c, bool host, const void* in, void* out, void* status, c
                    column(d.open, cols.open),
                    column(d.backdoors, cols.backdoors),
                    column(d.key, cols.key),
-                   column(d.open4, cols.open4)});
+                   column(d.open4, cols.open4),
+                   column(d.open5, cols.open5)});
     if ((rc = io.send()) || (rc = launch_grade(c, d_in, d_out, d_status, d, n, budget_arg(node_budget)))) return rc;
     return io.fetch();
 }
 
-// sdk_generate_graded, sdk_generate_rated, sdk_generate_subsets and their _dev forms: `g` is the call with
+// sdk_generate_graded, sdk_generate_rated, sdk_generate_subsets, sdk_generate_fish and their _dev forms: `g` is the call with
 // the caller's pointers (its n is set here, from the checked `n`).  host: they are host arrays, and the
 // rows found come back through the context's gg_out_* buffers; else they are device pointers.  The order
 // of the checks is the order of the errors a caller with several bad arguments sees.
@@ -1449,7 +1493,8 @@ int graded_call(sdk_ctx* c, bool host, size_t n, GradedCall g, uint64_t* found, 
     int rc;
     if ((rc = check_graded_args(g.first, n, g.level_mask, g.clues_lo, g.clues_hi, g.max_scan, g.chunk)) ||
         (g.rated && (rc = check_rated_range(g.bd_lo, g.bd_hi))) ||
-        (g.subsets && (rc = check_subsets_range(g.o4_lo, g.o4_hi))))
+        (g.subsets && (rc = check_subsets_range(g.o4_lo, g.o4_hi))) ||
+        (g.fish && ((rc = check_subsets_range(g.o4_lo, g.o4_hi)) || (rc = check_fish_range(g.o5_lo, g.o5_hi)))))
         return rc;
     if (!host) {
         if ((reinterpret_cast<uintptr_t>(g.puzzles) | reinterpret_cast<uintptr_t>(g.grids)) & 15u)
@@ -1468,7 +1513,8 @@ int graded_call(sdk_ctx* c, bool host, size_t n, GradedCall g, uint64_t* found, 
             if ((rc = ensure(c->gg_out_puz, rows * 81)) || (rc = ensure(c->gg_out_grid, rows * 81)) ||
                 (g.level && (rc = ensure(c->gg_out_level, rows))) || (g.open && (rc = ensure(c->gg_out_open, rows))) ||
                 (g.backdoors && (rc = ensure(c->gg_out_bd, rows))) || (g.key && (rc = ensure(c->gg_out_key, rows))) ||
-                (g.open4 && (rc = ensure(c->gg_out_o4, rows))) || (g.index && (rc = ensure(c->gg_out_index, rows * 8))))
+                (g.open4 && (rc = ensure(c->gg_out_o4, rows))) || (g.open5 && (rc = ensure(c->gg_out_o5, rows))) ||
+                (g.index && (rc = ensure(c->gg_out_index, rows * 8))))
                 return rc;
             d.puzzles = u8(c->gg_out_puz.p);
             d.grids = u8(c->gg_out_grid.p);
@@ -1477,6 +1523,7 @@ int graded_call(sdk_ctx* c, bool host, size_t n, GradedCall g, uint64_t* found, 
             d.backdoors = g.backdoors ? u8(c->gg_out_bd.p) : nullptr;
             d.key = g.key ? u8(c->gg_out_key.p) : nullptr;
             d.open4 = g.open4 ? u8(c->gg_out_o4.p) : nullptr;
+            d.open5 = g.open5 ? u8(c->gg_out_o5.p) : nullptr;
             d.index = g.index ? static_cast<uint64_t*>(c->gg_out_index.p) : nullptr;
         }
         if ((rc = launch_generate_graded(c, d, &f, &s))) return rc;
@@ -1490,7 +1537,8 @@ int graded_call(sdk_ctx* c, bool host, size_t n, GradedCall g, uint64_t* found, 
                            column(d.open, g.open),
                            column(d.backdoors, g.backdoors),
                            column(d.key, g.key),
-                           column(d.open4, g.open4)});
+                           column(d.open4, g.open4),
+                           column(d.open5, g.open5)});
             if ((rc = io.fetch())) return rc;
         }
     }
@@ -1519,6 +1567,16 @@ GradedCall subsets_args(GradedCall g, uint32_t lo, uint32_t hi, void* open4) {
     g.o4_lo = lo;
     g.o4_hi = hi;
     g.open4 = u8(open4);
+    return g;
+}
+GradedCall fish_args(GradedCall g, uint32_t lo4, uint32_t hi4, uint32_t lo5, uint32_t hi5, void* open4, void* open5) {
+    g.fish = true;
+    g.o4_lo = lo4;
+    g.o4_hi = hi4;
+    g.o5_lo = lo5;
+    g.o5_hi = hi5;
+    g.open4 = u8(open4);
+    g.open5 = u8(open5);
     return g;
 }
 
@@ -2360,6 +2418,19 @@ int sdk_subsets_batch(sdk_ctx* c, const uint8_t* in, uint8_t* out, int8_t* statu
     return grade_call(c, true, in, out, status, {level, open, nullptr, nullptr, open4}, n, node_budget);
 }
 
+int sdk_fish_batch_dev(sdk_ctx* c, const void* d_in, void* d_out, void* d_status, void* d_level, void* d_open,
+                       void* d_open4, void* d_open5, size_t n, uint64_t node_budget) {
+    if (!c || (n && (!d_in || !d_out || !d_status || !d_level || !d_open5))) return fail(SDK_EINVAL, "NULL argument");
+    return grade_call(c, false, d_in, d_out, d_status,
+                      {u8(d_level), u8(d_open), nullptr, nullptr, u8(d_open4), u8(d_open5)}, n, node_budget);
+}
+
+int sdk_fish_batch(sdk_ctx* c, const uint8_t* in, uint8_t* out, int8_t* status, uint8_t* level, uint8_t* open,
+                   uint8_t* open4, uint8_t* open5, size_t n, uint64_t node_budget) {
+    if (!c || (n && (!in || !out || !status || !level || !open5))) return fail(SDK_EINVAL, "NULL argument");
+    return grade_call(c, true, in, out, status, {level, open, nullptr, nullptr, open4, open5}, n, node_budget);
+}
+
 int sdk_canonical_batch_dev(sdk_ctx* c, const void* d_in, void* d_canon, void* d_solution, void* d_status,
                             void* d_gather, void* d_relabel, void* d_ties, size_t n, uint64_t node_budget) {
     if (!c || (n && (!d_in || !d_canon || !d_status))) return fail(SDK_EINVAL, "NULL argument");
@@ -2627,6 +2698,30 @@ int sdk_generate_subsets(sdk_ctx* c, uint64_t seed, uint64_t first, size_t n, ui
                        subsets_args(graded_args(seed, first, level_mask, clues_lo, clues_hi, max_scan, chunk, puzzles,
                                                 grids, level, open, index),
                                     open4_lo, open4_hi, open4),
+                       found, scanned);
+}
+
+int sdk_generate_fish_dev(sdk_ctx* c, uint64_t seed, uint64_t first, size_t n, uint32_t level_mask, uint32_t clues_lo,
+                          uint32_t clues_hi, uint32_t open4_lo, uint32_t open4_hi, uint32_t open5_lo,
+                          uint32_t open5_hi, uint64_t max_scan, uint64_t chunk, void* d_puzzles, void* d_grids,
+                          void* d_level, void* d_open, void* d_open4, void* d_open5, void* d_index, uint64_t* found,
+                          uint64_t* scanned) {
+    return graded_call(c, false, n,
+                       fish_args(graded_args(seed, first, level_mask, clues_lo, clues_hi, max_scan, chunk, d_puzzles,
+                                             d_grids, d_level, d_open, d_index),
+                                 open4_lo, open4_hi, open5_lo, open5_hi, d_open4, d_open5),
+                       found, scanned);
+}
+
+int sdk_generate_fish(sdk_ctx* c, uint64_t seed, uint64_t first, size_t n, uint32_t level_mask, uint32_t clues_lo,
+                      uint32_t clues_hi, uint32_t open4_lo, uint32_t open4_hi, uint32_t open5_lo, uint32_t open5_hi,
+                      uint64_t max_scan, uint64_t chunk, uint8_t* puzzles, uint8_t* grids, uint8_t* level,
+                      uint8_t* open, uint8_t* open4, uint8_t* open5, uint64_t* index, uint64_t* found,
+                      uint64_t* scanned) {
+    return graded_call(c, true, n,
+                       fish_args(graded_args(seed, first, level_mask, clues_lo, clues_hi, max_scan, chunk, puzzles,
+                                             grids, level, open, index),
+                                 open4_lo, open4_hi, open5_lo, open5_hi, open4, open5),
                        found, scanned);
 }
 

@@ -364,6 +364,27 @@ class SudokuEngine:
                 "sdk_subsets_batch")
         return status, level, open_, open4, out
 
+    def fish_batch(self, boards, budget=None):
+        """uint8[n,81] -> (status int8[n], level uint8[n], open uint8[n], open4 uint8[n], open5 uint8[n],
+        out uint8[n,81]): subsets_batch, and for every level-4 board the number of cells still open once
+        X-wings, swordfish and jellyfish (row and column fish of sizes 2..4) join the subsets
+        (sdk_fish_batch).  open4 > 0 and open5 == 0: the board needs a fish, and a fish is enough; open5 is
+        SDK_FISH_NONE = 0xFF for every board of another level.  status, level, open and out are exactly
+        grade_batch's, open4 is subsets_batch's.  Not sharded by MultiDeviceEngine or ShardedBatch: it runs
+        on this engine's device."""
+        boards = np.ascontiguousarray(boards, dtype=np.uint8).reshape(-1, 81)
+        n = boards.shape[0]
+        if budget is not None and not 0 <= int(budget) < (1 << 63):
+            raise ValueError("budget must be 0 (unlimited) or a positive node count")
+        out = np.empty_like(boards)
+        status = np.empty(n, dtype=np.int8)
+        level, open_, open4, open5 = (np.empty(n, dtype=np.uint8) for _ in range(4))
+        L.check(self.lib.sdk_fish_batch(self.ctx, _ptr(boards), _ptr(out), _ptr(status), _ptr(level), _ptr(open_),
+                                        _ptr(open4), _ptr(open5), n,
+                                        L.SDK_BUDGET_CONTEXT if budget is None else int(budget)),
+                "sdk_fish_batch")
+        return status, level, open_, open4, open5, out
+
     def canonical_batch(self, boards, budget=None):
         """uint8[n,81] -> (status int8[n], canon uint8[n,81], solution uint8[n,81], gather uint8[n,81],
         relabel uint8[n,10], ties uint16[n]): the canonical form of each board under the Sudoku
@@ -499,9 +520,10 @@ class SudokuEngine:
         return puzzles, grids, status
 
     @staticmethod
-    def _graded_args(n, levels, seed, lo, clues, max_scan, chunk, band=None):
+    def _graded_args(n, levels, seed, lo, clues, max_scan, chunk, band=None, band2=None):
         """The arguments of sdk_generate_graded from generate_graded's (ValueError for a bad one); band =
-        (name, range) adds the (lo, hi) of sdk_generate_rated's backdoors or sdk_generate_subsets' open4."""
+        (name, range) adds the (lo, hi) of sdk_generate_rated's backdoors or sdk_generate_subsets' open4,
+        band2 a second pair behind it (sdk_generate_fish's open5)."""
         n, seed, lo = SudokuEngine._stream_rows(n, seed, lo)
         if n >= 1 << 31:
             raise ValueError("n must be below 2^31")
@@ -521,17 +543,19 @@ class SudokuEngine:
             raise ValueError("chunk must be 0 (automatic) or 1..2^24")
         if band is None:
             return seed, lo, n, mask, clues_lo, clues_hi, max_scan, chunk
-        name, rng = band
-        f_lo, f_hi = (0, 64) if rng is None else (int(rng[0]), int(rng[1]))
-        if not 0 <= f_lo <= f_hi <= 64:
-            raise ValueError(f"{name} must be (lo, hi) with 0 <= lo <= hi <= 64")
-        return seed, lo, n, mask, clues_lo, clues_hi, f_lo, f_hi, max_scan, chunk
+        bands = []
+        for name, rng in (band,) if band2 is None else (band, band2):
+            f_lo, f_hi = (0, 64) if rng is None else (int(rng[0]), int(rng[1]))
+            if not 0 <= f_lo <= f_hi <= 64:
+                raise ValueError(f"{name} must be (lo, hi) with 0 <= lo <= hi <= 64")
+            bands += [f_lo, f_hi]
+        return (seed, lo, n, mask, clues_lo, clues_hi, *bands, max_scan, chunk)
 
     def _generate_selected(self, family, args, extra):
         """sdk_generate_<family> on host arrays of min(n, max_scan) rows, `extra` uint8 columns after
         level and open: (puzzles, solutions, level, open, *extra, index, scanned), `found` rows each."""
-        n, max_scan = args[2], args[-2]     # _graded_args: (seed, lo, n, mask, ..., max_scan, chunk) with or without a band
-        assert len(args) in (8, 10)
+        n, max_scan = args[2], args[-2]     # _graded_args: (seed, lo, n, mask, ..., max_scan, chunk) with or without bands
+        assert len(args) in (8, 10, 12)
         rows = min(n, max_scan)
         puzzles = np.empty((rows, 81), dtype=np.uint8)
         grids = np.empty((rows, 81), dtype=np.uint8)
@@ -585,6 +609,18 @@ class SudokuEngine:
         MultiDeviceEngine, like generate_graded and generate_rated."""
         args = self._graded_args(n, levels, seed, lo, clues, max_scan, chunk, ("open4", open4))
         return self._generate_selected("subsets", args, 1)
+
+    def generate_fish(self, n, levels=(1, 2, 3, 4), seed=synth.DEFAULT_SEED + 3, lo=0, clues=None, open4=None,
+                      open5=None, max_scan=1 << 26, chunk=0):
+        """generate_graded with a subsets and a fish filter (sdk_generate_fish): a level-4 puzzle is kept only
+        when its fish_batch counts lie in open4 = (lo, hi) and open5 = (lo, hi) (None: 0..64); puzzles of
+        levels 1..3 are not filtered by them.  levels=(4,), open4=(1, 64), open5=(0, 0): the puzzles that
+        need a fish, and for which a fish is enough.  Returns generate_graded's tuple with the counts after
+        open: (puzzles, solutions, level, open, open4 uint8[found], open5 uint8[found], index, scanned);
+        both are 0xFF for the puzzles of levels 1..3.  Not sharded by MultiDeviceEngine, like
+        generate_graded."""
+        args = self._graded_args(n, levels, seed, lo, clues, max_scan, chunk, ("open4", open4), ("open5", open5))
+        return self._generate_selected("fish", args, 2)
 
     def expand(self, boards, masks=None, target=64):
         """Lex-ordered frontier below `boards` (sdk_expand_boards): uint8[k,81], children in the
@@ -785,6 +821,15 @@ class SudokuEngine:
                                                L.SDK_BUDGET_CONTEXT if budget is None else int(budget)),
                 "sdk_subsets_batch_dev")
 
+    def fish_batch_dev(self, d_in, d_out, d_status, d_level, d_open5, n, d_open=None, d_open4=None, budget=None):
+        """fish_batch on device buffers: as grade_batch_dev (d_in and d_out 16-byte aligned, d_out may be
+        d_in), d_open5 required, d_open and d_open4 optional."""
+        L.check(self.lib.sdk_fish_batch_dev(self.ctx, d_in.ptr, d_out.ptr, d_status.ptr, d_level.ptr,
+                                            d_open.ptr if d_open else None, d_open4.ptr if d_open4 else None,
+                                            d_open5.ptr, int(n),
+                                            L.SDK_BUDGET_CONTEXT if budget is None else int(budget)),
+                "sdk_fish_batch_dev")
+
     def canonical_batch_dev(self, d_in, d_canon, d_status, n, d_solution=None, d_gather=None, d_relabel=None,
                             d_ties=None, budget=None):
         """canonical_batch on device buffers: d_in and d_canon 16-byte aligned (d_canon may be d_in);
@@ -845,6 +890,14 @@ class SudokuEngine:
         """generate_subsets into device buffers of n rows, as generate_graded_dev: -> (found, scanned)."""
         args = self._graded_args(n, levels, seed, lo, clues, max_scan, chunk, ("open4", open4))
         return self._generate_selected_dev("subsets", args, d_puzzles, d_grids, (d_level, d_open, d_open4), d_index)
+
+    def generate_fish_dev(self, d_puzzles, d_grids, n, levels=(1, 2, 3, 4), seed=synth.DEFAULT_SEED + 3, lo=0,
+                          clues=None, open4=None, open5=None, max_scan=1 << 26, chunk=0, d_level=None, d_open=None,
+                          d_open4=None, d_open5=None, d_index=None):
+        """generate_fish into device buffers of n rows, as generate_graded_dev: -> (found, scanned)."""
+        args = self._graded_args(n, levels, seed, lo, clues, max_scan, chunk, ("open4", open4), ("open5", open5))
+        return self._generate_selected_dev("fish", args, d_puzzles, d_grids, (d_level, d_open, d_open4, d_open5),
+                                           d_index)
 
     def select_rows_dev(self, rows):
         """One round of the graded selection on caller-supplied device rows (sdk_select_rows_dev): `rows`

@@ -18,9 +18,9 @@
  *       -> sdk_count_solutions
  *   (no reference counterpart: a batch's verdicts, the technique a board needs,
  *   and inside the search level the number of single-cell backdoors)
- *       -> sdk_classify_batch, sdk_grade_batch, sdk_rate_batch, sdk_subsets_batch
+ *       -> sdk_classify_batch, sdk_grade_batch, sdk_rate_batch, sdk_subsets_batch, sdk_fish_batch
  *       -> sdk_generate_puzzles, sdk_generate_graded, sdk_generate_rated,
- *          sdk_generate_subsets, sdk_minimize_level_batch, sdk_generate_level
+ *          sdk_generate_subsets, sdk_generate_fish, sdk_minimize_level_batch, sdk_generate_level
  *   DFS subtree split across ring nodes (NEEDWORK/TASK, DHT_Node.py:491-510,
  *   225-250; utils.py:1-9) -- within one node of GPUs:
  *       -> sdk_frontier_* + sdk_comm_* (RCCL over xGMI)
@@ -58,6 +58,7 @@ extern "C" {
                             /* and sdk_minimize_level_batch[_dev], sdk_generate_level[_dev]       */
                             /* and sdk_select_rows_dev                                            */
                             /* and sdk_canonical_batch[_dev]                                      */
+                            /* and sdk_fish_batch[_dev] and sdk_generate_fish[_dev]               */
                             /* (new symbols only: nothing a version-2 caller uses changed)        */
 
 /* return codes */
@@ -340,6 +341,36 @@ int sdk_rate_batch(sdk_ctx *ctx, const uint8_t *in, uint8_t *out, int8_t *status
 int sdk_subsets_batch(sdk_ctx *ctx, const uint8_t *in, uint8_t *out, int8_t *status, uint8_t *level,
                       uint8_t *open, uint8_t *open4, size_t n, uint64_t node_budget);
 
+/* Basic fish inside level SDK_GRADE_SEARCH: what do X-wings, swordfish and jellyfish leave open?
+ *
+ * On the candidate sets of sdk_grade_batch.  For a digit d, M_d is the 9 x 9 bit matrix whose row r holds
+ * the columns c at which cell (r, c) still has candidate d; closed cells are included.
+ *   row fish of size k     k rows of M_d whose union has at most k columns: every other row loses those
+ *                          columns, that is, the cells lose candidate d;
+ *   column fish of size k  the same on the transpose of M_d.
+ * k = 1 is a hidden single of a line followed by N; k = 2, 3, 4 are X-wing, swordfish, jellyfish.  Finned,
+ * sashimi and franken fish are not part of it.  R5 = R4 + {row and column fish of sizes 2..4, every
+ * digit}, and F_5 is its fixpoint.  A fish removes no digit of a completion (Hall's condition on the
+ * digit's places) and its premise survives further removals, so the argument above carries over: F_5 is
+ * one state whatever the order of application, a pure function of the board.  A row fish of size k among
+ * the m rows where d is not yet placed removes what the column fish of size m - k removes; with m <= 9,
+ * sizes up to 4 on both orientations cover every size.
+ *   open5   uint8[n], required.  For a board of level SDK_GRADE_SEARCH the number of open cells of
+ *           F_5, 0..64; 0 with open4 > 0: the board needs a fish, and a fish is enough.  SDK_FISH_NONE for
+ *           every board of any other level, a board whose search hit the node budget (level
+ *           SDK_GRADE_NONE) included.
+ *   open4   uint8[n], nullable: sdk_subsets_batch's column, byte for byte.
+ *   status, out, level, open  exactly sdk_grade_batch's, byte for byte, under every option and
+ *           budget (open nullable).
+ * The call is a grade call with one more stage per slice, in the place of the subsets stage
+ * (fish_kernel.h: one level-4 board per half-wave; the subsets stage's rounds to F_4, where open4 is
+ * taken, then rounds in which nine lanes take a digit each).  It changes no option and leaves
+ * SDK_OPT_PROP32_UNDECIDED as a grade call does.  Any n up to 2^31-1 (slices of 2^24 boards); one span
+ * under SDK_OPT_TIMING. */
+#define SDK_FISH_NONE 0xFFu
+int sdk_fish_batch(sdk_ctx *ctx, const uint8_t *in, uint8_t *out, int8_t *status, uint8_t *level,
+                   uint8_t *open, uint8_t *open4, uint8_t *open5, size_t n, uint64_t node_budget);
+
 /* Canonical forms for n boards: are two boards the same puzzle under the Sudoku symmetries?
  *
  * A symmetry is a pair (g, rho).  g is a permutation of the cells 0..80 (new cell -> old cell) made of a
@@ -530,6 +561,26 @@ int sdk_generate_subsets(sdk_ctx *ctx, uint64_t seed, uint64_t first, size_t n,
                          uint8_t *open4,
                          uint64_t *index, uint64_t *found, uint64_t *scanned);
 
+/* Puzzles of a requested grade, subsets count and fish count: sdk_generate_graded with two more
+ * conditions.  Candidate k is a hit when it is a hit of sdk_generate_graded(level_mask, clues_lo,
+ * clues_hi) and, if its level is SDK_GRADE_SEARCH, open4_lo <= open4 <= open4_hi and open5_lo <= open5 <=
+ * open5_hi (sdk_fish_batch's counts with no node budget).  Candidates of levels 1..3 are not filtered by
+ * the ranges.  open4 = (1, 64), open5 = (0, 0) with level_mask = 1 << SDK_GRADE_SEARCH: the puzzles that
+ * need a fish, and for which a fish is enough.
+ *   open4_lo <= open4_hi <= 64 and open5_lo <= open5_hi <= 64, else SDK_EINVAL;
+ *   open4, open5  uint8[n], nullable: the hits' counts (0xFF for levels 1..3).
+ * Everything else is sdk_generate_graded's: the window, found, scanned, chunk (speed only), the
+ * purity of the result (now also a function of the ranges), one 8-byte readback per round, one span.
+ * A round grades with the fish stage; when level_mask lacks SDK_GRADE_SEARCH the stage is skipped.
+ * With both ranges (0, 64) the shared outputs are sdk_generate_graded's, byte for byte. */
+int sdk_generate_fish(sdk_ctx *ctx, uint64_t seed, uint64_t first, size_t n,
+                      uint32_t level_mask, uint32_t clues_lo, uint32_t clues_hi,
+                      uint32_t open4_lo, uint32_t open4_hi, uint32_t open5_lo, uint32_t open5_hi,
+                      uint64_t max_scan, uint64_t chunk,
+                      uint8_t *puzzles, uint8_t *grids, uint8_t *level, uint8_t *open,
+                      uint8_t *open4, uint8_t *open5,
+                      uint64_t *index, uint64_t *found, uint64_t *scanned);
+
 /* The worklist step of a resumable lex-first search of a board whose solve hit the
  * budget (distributed_sudoku_solver_amd/search.py; the in-node form of handing a
  * subtree on, DHT_Node.py:491-510): expand n boards -- board i with first-cell mask
@@ -693,6 +744,10 @@ int sdk_rate_batch_dev(sdk_ctx *ctx, const void *d_in, void *d_out, void *d_stat
  * or NULL. */
 int sdk_subsets_batch_dev(sdk_ctx *ctx, const void *d_in, void *d_out, void *d_status, void *d_level,
                           void *d_open, void *d_open4, size_t n, uint64_t node_budget);
+/* as sdk_grade_batch_dev (alignment, d_out may be d_in); d_open5 uint8[n] required, d_open and d_open4
+ * uint8[n] or NULL. */
+int sdk_fish_batch_dev(sdk_ctx *ctx, const void *d_in, void *d_out, void *d_status, void *d_level,
+                       void *d_open, void *d_open4, void *d_open5, size_t n, uint64_t node_budget);
 /* d_in and d_canon 16-byte aligned, else SDK_EINVAL; d_canon may be d_in (exactly).  d_solution, d_gather,
  * d_relabel and d_ties (uint16[n]) or NULL; a d_solution that is not 16-byte aligned only skips the
  * propagation pass, as in sdk_classify_batch_dev. */
@@ -737,6 +792,14 @@ int sdk_generate_subsets_dev(sdk_ctx *ctx, uint64_t seed, uint64_t first, size_t
                              void *d_puzzles, void *d_grids, void *d_level, void *d_open,
                              void *d_open4,
                              void *d_index, uint64_t *found, uint64_t *scanned);
+/* as sdk_generate_graded_dev; d_open4 and d_open5 uint8[n] or NULL */
+int sdk_generate_fish_dev(sdk_ctx *ctx, uint64_t seed, uint64_t first, size_t n,
+                          uint32_t level_mask, uint32_t clues_lo, uint32_t clues_hi,
+                          uint32_t open4_lo, uint32_t open4_hi, uint32_t open5_lo, uint32_t open5_hi,
+                          uint64_t max_scan, uint64_t chunk,
+                          void *d_puzzles, void *d_grids, void *d_level, void *d_open,
+                          void *d_open4, void *d_open5,
+                          void *d_index, uint64_t *found, uint64_t *scanned);
 
 /* One round of the selection behind sdk_generate_graded / _rated / _subsets (select_kernel.h), on rows
  * the caller supplies instead of rows the generator and the grader made: the seam through which the
