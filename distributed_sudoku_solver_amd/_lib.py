@@ -39,6 +39,8 @@ SDK_RATE_NONE = 0xFF
 SDK_SUBSETS_NONE = 0xFF
 # sdk_fish_batch: open5 of a board that is not of level SDK_GRADE_SEARCH
 SDK_FISH_NONE = 0xFF
+# sdk_wings_batch: open6 of a board that is not of level SDK_GRADE_SEARCH
+SDK_WINGS_NONE = 0xFF
 
 SDK_CHECK_OK = 1
 SDK_CHECK_RAW_NAMEERROR = 2
@@ -146,6 +148,8 @@ SIGNATURES = {
     "sdk_subsets_batch_dev": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, ctypes.c_uint64]),
     "sdk_fish_batch": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, ctypes.c_uint64]),
     "sdk_fish_batch_dev": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, ctypes.c_uint64]),
+    "sdk_wings_batch": (ctypes.c_int, [_vp] * 9 + [_sz, ctypes.c_uint64]),
+    "sdk_wings_batch_dev": (ctypes.c_int, [_vp] * 9 + [_sz, ctypes.c_uint64]),
     # (ctx, in, canon, solution, status, gather, relabel, ties, n, node_budget)
     "sdk_canonical_batch": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, ctypes.c_uint64]),
     "sdk_canonical_batch_dev": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, ctypes.c_uint64]),
@@ -190,6 +194,12 @@ SIGNATURES = {
     "sdk_generate_fish_dev": (ctypes.c_int, [_vp, ctypes.c_uint64, ctypes.c_uint64, _sz] + [ctypes.c_uint32] * 7 +
                               [ctypes.c_uint64, ctypes.c_uint64] + [_vp] * 7 +
                               [ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]),
+    "sdk_generate_wings": (ctypes.c_int, [_vp, ctypes.c_uint64, ctypes.c_uint64, _sz] + [ctypes.c_uint32] * 7 +
+                           [ctypes.c_uint64, ctypes.c_uint64] + [_vp] * 7 +
+                           [ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]),
+    "sdk_generate_wings_dev": (ctypes.c_int, [_vp, ctypes.c_uint64, ctypes.c_uint64, _sz] + [ctypes.c_uint32] * 7 +
+                               [ctypes.c_uint64, ctypes.c_uint64] + [_vp] * 7 +
+                               [ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]),
     "sdk_select_rows_dev": (ctypes.c_int, [_vp, ctypes.POINTER(SelectRows), ctypes.POINTER(ctypes.c_uint64),
                                            ctypes.POINTER(ctypes.c_uint64)]),
     "sdk_frontier_boards_dev": (ctypes.c_int, [_vp, ctypes.POINTER(_vp), ctypes.POINTER(ctypes.c_uint64)]),

@@ -18,6 +18,7 @@
 #include "select_args.h"
 #include "solve_args.h"
 #include "subsets_args.h"
+#include "wings_args.h"
 
 namespace sdk {
 
@@ -55,6 +56,9 @@ hipError_t launch_subsets32(const Subsets32Args& a, unsigned grid, hipStream_t s
 
 // fish_launch.hip: the same work items and layout, with the fish rounds and both counts
 hipError_t launch_fish32(const Fish32Args& a, unsigned grid, hipStream_t stream);
+
+// wings_launch.hip: the same again, with the wide rounds (wings and simple colouring) and three counts
+hipError_t launch_wings32(const Wings32Args& a, unsigned grid, hipStream_t stream);
 
 // canon_launch.hip: one wave per board (grid-stride over the slice)
 hipError_t launch_canon(const CanonArgs& a, unsigned grid, hipStream_t stream);

@@ -196,6 +196,8 @@ struct sdk_ctx {
     DevBuf s4_open4, gg_o4, gg_out_o4;   // sdk_subsets_batch (host pointers); sdk_generate_subsets: a round's, the host call's
     DevBuf f5_open5, gg_o5, gg_out_o5;   // sdk_fish_batch, sdk_generate_fish: the same for open5 (open4 goes through the above)
     DevBuf f5_open4;                     // the fish stage's open4 of a slice where the caller wants none
+    DevBuf w6_open6, gg_o6, gg_out_o6;   // sdk_wings_batch, sdk_generate_wings: the same for open6
+    DevBuf w6_open5;                     // the wings stage's open5 of a slice where the caller wants none (open4: f5_open4)
     DevBuf cn_sol;                 // sdk_canonical_batch_dev without a solution buffer: a slice's completions
     DevBuf cn_gather, cn_relabel, cn_ties;   // sdk_canonical_batch: the host-pointer call's symmetries and tie counts
     DevBuf fr_a, fr_b, prop, bcell, bmask, nchild, offs, fr_status, fr_mask, tsum, fr_ctl;
@@ -314,14 +316,14 @@ struct Piece {
 };
 
 // The copies of a host-pointer call: send() before the launch, fetch() after it (it synchronizes).
-// The (at most nine: sdk_generate_fish) pieces lie in the pinned area (HostBuf) in the order given -- widest element
+// The (at most ten: sdk_generate_wings) pieces lie in the pinned area (HostBuf) in the order given -- widest element
 // type first, so every slot is aligned for its type; a call too large for the area copies straight
 // from / to the caller's pageable memory.  An error return between send() and the end of fetch()
 // may leave copies from / into the area queued, so the stream is drained first: the next call's
 // memcpy into the area (or a grow that frees it) cannot race them.
 class Staging {
     sdk_ctx* c;
-    Piece p[9];
+    Piece p[10];
     int np = 0;
     bool armed = true;
 
@@ -886,19 +888,25 @@ int launch_classify(sdk_ctx* c, const uint8_t* d_in, uint8_t* d_out, int8_t* d_s
 // place of it -- it computes both counts.  Both columns filled with 0xFF, the same counter cleared, the
 // same grid (one half-wave per level-4 board of the list, four waves per SIMD).  d_open4 null: the slice's
 // open4 goes to the context's f5_open4.  Without the pointer nothing of it is enqueued.
+// d_open6 non-null (sdk_wings_batch; wings_kernel.h): the wings stage, where the fish stage sits and in place
+// of it -- it computes all three counts.  The three columns filled with 0xFF, the same counter cleared, the
+// fish stage's grid.  d_open4 or d_open5 null: the slice's counts go to the context's f5_open4 / w6_open5.
+// Without the pointer nothing of it is enqueued.
 // The columns of a grade call beside out and status, one byte per board: level always, the others nullable.
 struct GradeCols {
     uint8_t *level, *open;
     uint8_t *backdoors, *key;   // the rate stage (sdk_rate_batch)
     uint8_t* open4;             // the subsets stage (sdk_subsets_batch)
     uint8_t* open5 = nullptr;   // the fish stage (sdk_fish_batch), which fills open4 too
+    uint8_t* open6 = nullptr;   // the wings stage (sdk_wings_batch), which fills open4 and open5 too
 };
 
 int launch_grade(sdk_ctx* c, const uint8_t* d_in, uint8_t* d_out, int8_t* d_status, const GradeCols& cols, size_t n,
                  int64_t budget) {
     if (n == 0) return SDK_OK;
     uint8_t *const d_level = cols.level, *const d_open = cols.open, *const d_bd = cols.backdoors,
-                   *const d_key = cols.key, *const d_open4 = cols.open4, *const d_open5 = cols.open5;
+                   *const d_key = cols.key, *const d_open4 = cols.open4, *const d_open5 = cols.open5,
+                   *const d_open6 = cols.open6;
     if ((reinterpret_cast<uintptr_t>(d_in) | reinterpret_cast<uintptr_t>(d_out)) & 15u)
         return fail(SDK_EINVAL, "device boards must be 16-byte aligned");
     if (budget < 0) budget = (int64_t)c->budget;
@@ -906,7 +914,9 @@ int launch_grade(sdk_ctx* c, const uint8_t* d_in, uint8_t* d_out, int8_t* d_stat
     const bool in_place = d_in == d_out;
     int rc;
     if ((rc = p32_reserve(c, cap)) || (in_place && (rc = ensure(c->gr_in, cap * 81))) ||
-        (!d_open && (rc = ensure(c->gr_open, cap))) || (d_open5 && !d_open4 && (rc = ensure(c->f5_open4, cap))))
+        (!d_open && (rc = ensure(c->gr_open, cap))) ||
+        ((d_open5 || d_open6) && !d_open4 && (rc = ensure(c->f5_open4, cap))) ||
+        (d_open6 && !d_open5 && (rc = ensure(c->w6_open5, cap))))
         return rc;
     TimedSpan span(c);
     if ((rc = span.begin())) return rc;
@@ -951,7 +961,24 @@ int launch_grade(sdk_ctx* c, const uint8_t* d_in, uint8_t* d_out, int8_t* d_stat
             if (sdk::launch_rate32(r, grid_for(c, m, 1, 16), c->stream) != hipSuccess)
                 rc = fail(SDK_EHIP, "rate launch failed");
         }
-        if (!rc && d_open5) {
+        if (!rc && d_open6) {
+            sdk::Wings32Args w{};
+            w.in = in;
+            w.level = a.level;
+            w.list = a.p.list;
+            w.n = m;
+            w.next = a.p.heads;
+            w.open4 = d_open4 ? d_open4 + b0 : static_cast<uint8_t*>(c->f5_open4.p);
+            w.open5 = d_open5 ? d_open5 + b0 : static_cast<uint8_t*>(c->w6_open5.p);
+            w.open6 = d_open6 + b0;
+            HIPCALL(hipMemsetAsync(w.open4, 0xFF, m, c->stream));
+            HIPCALL(hipMemsetAsync(w.open5, 0xFF, m, c->stream));
+            HIPCALL(hipMemsetAsync(w.open6, 0xFF, m, c->stream));
+            HIPCALL(hipMemsetAsync(w.next, 0, 4, c->stream));
+            // four waves per SIMD; at most one wave per two listed boards
+            if (sdk::launch_wings32(w, grid_for(c, m, 2, 16), c->stream) != hipSuccess)
+                rc = fail(SDK_EHIP, "wings launch failed");
+        } else if (!rc && d_open5) {
             sdk::Fish32Args f{};
             f.in = in;
             f.level = a.level;
@@ -1224,6 +1251,10 @@ struct GradedCall {
     bool fish = false;
     uint32_t o5_lo = 0, o5_hi = 64;
     uint8_t* open5 = nullptr;
+    // sdk_generate_wings: both o5_lo <= open5 <= o5_hi and o6_lo <= open6 <= o6_hi, and the wings stage
+    bool wings = false;
+    uint32_t o6_lo = 0, o6_hi = 64;
+    uint8_t* open6 = nullptr;
 };
 
 // One round's selection (select_kernel.h): rows [0, m) of caller-supplied buffers -- a round of
@@ -1345,9 +1376,13 @@ int launch_generate_graded(sdk_ctx* c, const GradedCall& g, uint64_t* found, uin
         uint8_t* key = rate ? static_cast<uint8_t*>(c->gg_key.p) : nullptr;
         const bool fish = g.fish && (g.level_mask >> SDK_GRADE_SEARCH & 1u);
         const bool subsets = fish || (g.subsets && (g.level_mask >> SDK_GRADE_SEARCH & 1u));
-        if ((subsets && (rc = ensure(c->gg_o4, rows))) || (fish && (rc = ensure(c->gg_o5, rows)))) return rc;
+        const bool wings = g.wings && (g.level_mask >> SDK_GRADE_SEARCH & 1u);
+        if ((subsets && (rc = ensure(c->gg_o4, rows))) || ((fish || wings) && (rc = ensure(c->gg_o5, rows))) ||
+            (wings && (rc = ensure(c->gg_o6, rows))))
+            return rc;
         uint8_t* o4 = subsets ? static_cast<uint8_t*>(c->gg_o4.p) : nullptr;
-        uint8_t* o5 = fish ? static_cast<uint8_t*>(c->gg_o5.p) : nullptr;
+        uint8_t* o5 = (fish || wings) ? static_cast<uint8_t*>(c->gg_o5.p) : nullptr;
+        uint8_t* o6 = wings ? static_cast<uint8_t*>(c->gg_o6.p) : nullptr;
         uint8_t* puz = static_cast<uint8_t*>(c->gg_puz.p);
         uint8_t* grid = static_cast<uint8_t*>(c->gg_grid.p);
         int8_t* st = static_cast<int8_t*>(c->gg_st.p);
@@ -1355,7 +1390,7 @@ int launch_generate_graded(sdk_ctx* c, const GradedCall& g, uint64_t* found, uin
         uint8_t* open = static_cast<uint8_t*>(c->gg_open.p);
         if ((rc = launch_generate_puzzles(c, g.seed, g.first + done, m, puz, grid, st)) ||
             (rc = launch_grade(c, puz, static_cast<uint8_t*>(c->gg_sol.p), static_cast<int8_t*>(c->gg_gst.p),
-                               GradeCols{level, open, bd, key, o4, o5}, m, 0)))
+                               GradeCols{level, open, bd, key, o4, o5, o6}, m, 0)))
             return rc;
         SelectRound r{};
         r.puzzles = puz;
@@ -1392,6 +1427,18 @@ int launch_generate_graded(sdk_ctx* c, const GradedCall& g, uint64_t* found, uin
             r.bd_lo = g.o5_lo;
             r.bd_hi = g.o5_hi;
             r.out_backdoors = g.open5;
+        }
+        if (g.wings) {
+            // The same slots once more: a wings call's open6 column and range go through the `backdoors` slot
+            // with `key` null, its open5 and range through the `open4` slot (open4 itself is not filtered).
+            r.backdoors = o6;
+            r.bd_lo = g.o6_lo;
+            r.bd_hi = g.o6_hi;
+            r.out_backdoors = g.open6;
+            r.open4 = o5;
+            r.o4_lo = g.o5_lo;
+            r.o4_hi = g.o5_hi;
+            r.out_open4 = g.open5;
         }
         if ((rc = launch_select_round(c, r, d_word))) return rc;
         sdk::SelWord word;
@@ -1442,10 +1489,16 @@ int check_fish_range(uint32_t lo, uint32_t hi) {
     return SDK_OK;
 }
 
+// ... and the open6 range of sdk_generate_wings
+int check_wings_range(uint32_t lo, uint32_t hi) {
+    if (lo > hi || hi > 64) return fail(SDK_EINVAL, "open6 range must be open6_lo <= open6_hi <= 64");
+    return SDK_OK;
+}
+
 uint8_t* u8(void* p) { return static_cast<uint8_t*>(p); }
 
-// sdk_grade_batch, sdk_rate_batch, sdk_subsets_batch, sdk_fish_batch and their _dev forms, behind each one's own test of
-// its required pointers: `cols` holds the columns the entry point has, the others null.  host: the pointers
+// sdk_grade_batch, sdk_rate_batch, sdk_subsets_batch, sdk_fish_batch, sdk_wings_batch and their _dev forms, behind each
+// one's own test of its required pointers: `cols` holds the columns the entry point has, the others null.  host: the pointers
 // are the caller's arrays, staged through the context's buffers (the same ones whichever family calls);
 // else they are device pointers and the call only enqueues.
 int grade_call(sdk_ctx* c, bool host, const void* in, void* out, void* status, const GradeCols& cols, size_t n,
@@ -1462,14 +1515,16 @@ int grade_call(sdk_ctx* c, bool host, const void* in, void* out, void* status, c
     if ((rc = ensure(c->in, n * 81)) || (rc = ensure(c->out, n * 81)) || (rc = ensure(c->status, n)) ||
         (rc = ensure(c->gr_level, n)) || (cols.open && (rc = ensure(c->gr_open, n))) ||
         (cols.backdoors && (rc = ensure(c->rt_bd, n))) || (cols.key && (rc = ensure(c->rt_key, n))) ||
-        (cols.open4 && (rc = ensure(c->s4_open4, n))) || (cols.open5 && (rc = ensure(c->f5_open5, n))))
+        (cols.open4 && (rc = ensure(c->s4_open4, n))) || (cols.open5 && (rc = ensure(c->f5_open5, n))) ||
+        (cols.open6 && (rc = ensure(c->w6_open6, n))))
         return rc;
     uint8_t* d_in = u8(c->in.p);
     uint8_t* d_out = u8(c->out.p);
     int8_t* d_status = static_cast<int8_t*>(c->status.p);
     const GradeCols d{u8(c->gr_level.p), cols.open ? u8(c->gr_open.p) : nullptr,
                       cols.backdoors ? u8(c->rt_bd.p) : nullptr, cols.key ? u8(c->rt_key.p) : nullptr,
-                      cols.open4 ? u8(c->s4_open4.p) : nullptr, cols.open5 ? u8(c->f5_open5.p) : nullptr};
+                      cols.open4 ? u8(c->s4_open4.p) : nullptr, cols.open5 ? u8(c->f5_open5.p) : nullptr,
+                      cols.open6 ? u8(c->w6_open6.p) : nullptr};
     // a column comes back iff the caller has it (a slot each, present or not)
     auto column = [n](const uint8_t* dev, uint8_t* dst) { return Piece{dst ? n : 0, nullptr, nullptr, dev, dst}; };
     Staging io(c, {{n * 81, in, d_in, d_out, out},
@@ -1479,13 +1534,14 @@ int grade_call(sdk_ctx* c, bool host, const void* in, void* out, void* status, c
                    column(d.backdoors, cols.backdoors),
                    column(d.key, cols.key),
                    column(d.open4, cols.open4),
-                   column(d.open5, cols.open5)});
+                   column(d.open5, cols.open5),
+                   column(d.open6, cols.open6)});
     if ((rc = io.send()) || (rc = launch_grade(c, d_in, d_out, d_status, d, n, budget_arg(node_budget)))) return rc;
     return io.fetch();
 }
 
-// sdk_generate_graded, sdk_generate_rated, sdk_generate_subsets, sdk_generate_fish and their _dev forms: `g` is the call with
-// the caller's pointers (its n is set here, from the checked `n`).  host: they are host arrays, and the
+// sdk_generate_graded, sdk_generate_rated, sdk_generate_subsets, sdk_generate_fish, sdk_generate_wings and their _dev forms:
+// `g` is the call with the caller's pointers (its n is set here, from the checked `n`).  host: they are host arrays, and the
 // rows found come back through the context's gg_out_* buffers; else they are device pointers.  The order
 // of the checks is the order of the errors a caller with several bad arguments sees.
 int graded_call(sdk_ctx* c, bool host, size_t n, GradedCall g, uint64_t* found, uint64_t* scanned) {
@@ -1494,7 +1550,8 @@ int graded_call(sdk_ctx* c, bool host, size_t n, GradedCall g, uint64_t* found, 
     if ((rc = check_graded_args(g.first, n, g.level_mask, g.clues_lo, g.clues_hi, g.max_scan, g.chunk)) ||
         (g.rated && (rc = check_rated_range(g.bd_lo, g.bd_hi))) ||
         (g.subsets && (rc = check_subsets_range(g.o4_lo, g.o4_hi))) ||
-        (g.fish && ((rc = check_subsets_range(g.o4_lo, g.o4_hi)) || (rc = check_fish_range(g.o5_lo, g.o5_hi)))))
+        (g.fish && ((rc = check_subsets_range(g.o4_lo, g.o4_hi)) || (rc = check_fish_range(g.o5_lo, g.o5_hi)))) ||
+        (g.wings && ((rc = check_fish_range(g.o5_lo, g.o5_hi)) || (rc = check_wings_range(g.o6_lo, g.o6_hi)))))
         return rc;
     if (!host) {
         if ((reinterpret_cast<uintptr_t>(g.puzzles) | reinterpret_cast<uintptr_t>(g.grids)) & 15u)
@@ -1514,6 +1571,7 @@ int graded_call(sdk_ctx* c, bool host, size_t n, GradedCall g, uint64_t* found, 
                 (g.level && (rc = ensure(c->gg_out_level, rows))) || (g.open && (rc = ensure(c->gg_out_open, rows))) ||
                 (g.backdoors && (rc = ensure(c->gg_out_bd, rows))) || (g.key && (rc = ensure(c->gg_out_key, rows))) ||
                 (g.open4 && (rc = ensure(c->gg_out_o4, rows))) || (g.open5 && (rc = ensure(c->gg_out_o5, rows))) ||
+                (g.open6 && (rc = ensure(c->gg_out_o6, rows))) ||
                 (g.index && (rc = ensure(c->gg_out_index, rows * 8))))
                 return rc;
             d.puzzles = u8(c->gg_out_puz.p);
@@ -1524,6 +1582,7 @@ int graded_call(sdk_ctx* c, bool host, size_t n, GradedCall g, uint64_t* found, 
             d.key = g.key ? u8(c->gg_out_key.p) : nullptr;
             d.open4 = g.open4 ? u8(c->gg_out_o4.p) : nullptr;
             d.open5 = g.open5 ? u8(c->gg_out_o5.p) : nullptr;
+            d.open6 = g.open6 ? u8(c->gg_out_o6.p) : nullptr;
             d.index = g.index ? static_cast<uint64_t*>(c->gg_out_index.p) : nullptr;
         }
         if ((rc = launch_generate_graded(c, d, &f, &s))) return rc;
@@ -1538,7 +1597,8 @@ int graded_call(sdk_ctx* c, bool host, size_t n, GradedCall g, uint64_t* found, 
                            column(d.backdoors, g.backdoors),
                            column(d.key, g.key),
                            column(d.open4, g.open4),
-                           column(d.open5, g.open5)});
+                           column(d.open5, g.open5),
+                           column(d.open6, g.open6)});
             if ((rc = io.fetch())) return rc;
         }
     }
@@ -1577,6 +1637,17 @@ GradedCall fish_args(GradedCall g, uint32_t lo4, uint32_t hi4, uint32_t lo5, uin
     g.o5_hi = hi5;
     g.open4 = u8(open4);
     g.open5 = u8(open5);
+    return g;
+}
+
+GradedCall wings_args(GradedCall g, uint32_t lo5, uint32_t hi5, uint32_t lo6, uint32_t hi6, void* open5, void* open6) {
+    g.wings = true;
+    g.o5_lo = lo5;
+    g.o5_hi = hi5;
+    g.o6_lo = lo6;
+    g.o6_hi = hi6;
+    g.open5 = u8(open5);
+    g.open6 = u8(open6);
     return g;
 }
 
@@ -2418,6 +2489,20 @@ int sdk_subsets_batch(sdk_ctx* c, const uint8_t* in, uint8_t* out, int8_t* statu
     return grade_call(c, true, in, out, status, {level, open, nullptr, nullptr, open4}, n, node_budget);
 }
 
+int sdk_wings_batch_dev(sdk_ctx* c, const void* d_in, void* d_out, void* d_status, void* d_level, void* d_open,
+                        void* d_open4, void* d_open5, void* d_open6, size_t n, uint64_t node_budget) {
+    if (!c || (n && (!d_in || !d_out || !d_status || !d_level || !d_open6))) return fail(SDK_EINVAL, "NULL argument");
+    return grade_call(c, false, d_in, d_out, d_status,
+                      {u8(d_level), u8(d_open), nullptr, nullptr, u8(d_open4), u8(d_open5), u8(d_open6)}, n,
+                      node_budget);
+}
+
+int sdk_wings_batch(sdk_ctx* c, const uint8_t* in, uint8_t* out, int8_t* status, uint8_t* level, uint8_t* open,
+                    uint8_t* open4, uint8_t* open5, uint8_t* open6, size_t n, uint64_t node_budget) {
+    if (!c || (n && (!in || !out || !status || !level || !open6))) return fail(SDK_EINVAL, "NULL argument");
+    return grade_call(c, true, in, out, status, {level, open, nullptr, nullptr, open4, open5, open6}, n, node_budget);
+}
+
 int sdk_fish_batch_dev(sdk_ctx* c, const void* d_in, void* d_out, void* d_status, void* d_level, void* d_open,
                        void* d_open4, void* d_open5, size_t n, uint64_t node_budget) {
     if (!c || (n && (!d_in || !d_out || !d_status || !d_level || !d_open5))) return fail(SDK_EINVAL, "NULL argument");
@@ -2698,6 +2783,30 @@ int sdk_generate_subsets(sdk_ctx* c, uint64_t seed, uint64_t first, size_t n, ui
                        subsets_args(graded_args(seed, first, level_mask, clues_lo, clues_hi, max_scan, chunk, puzzles,
                                                 grids, level, open, index),
                                     open4_lo, open4_hi, open4),
+                       found, scanned);
+}
+
+int sdk_generate_wings_dev(sdk_ctx* c, uint64_t seed, uint64_t first, size_t n, uint32_t level_mask, uint32_t clues_lo,
+                           uint32_t clues_hi, uint32_t open5_lo, uint32_t open5_hi, uint32_t open6_lo,
+                           uint32_t open6_hi, uint64_t max_scan, uint64_t chunk, void* d_puzzles, void* d_grids,
+                           void* d_level, void* d_open, void* d_open5, void* d_open6, void* d_index, uint64_t* found,
+                           uint64_t* scanned) {
+    return graded_call(c, false, n,
+                       wings_args(graded_args(seed, first, level_mask, clues_lo, clues_hi, max_scan, chunk, d_puzzles,
+                                              d_grids, d_level, d_open, d_index),
+                                  open5_lo, open5_hi, open6_lo, open6_hi, d_open5, d_open6),
+                       found, scanned);
+}
+
+int sdk_generate_wings(sdk_ctx* c, uint64_t seed, uint64_t first, size_t n, uint32_t level_mask, uint32_t clues_lo,
+                       uint32_t clues_hi, uint32_t open5_lo, uint32_t open5_hi, uint32_t open6_lo, uint32_t open6_hi,
+                       uint64_t max_scan, uint64_t chunk, uint8_t* puzzles, uint8_t* grids, uint8_t* level,
+                       uint8_t* open, uint8_t* open5, uint8_t* open6, uint64_t* index, uint64_t* found,
+                       uint64_t* scanned) {
+    return graded_call(c, true, n,
+                       wings_args(graded_args(seed, first, level_mask, clues_lo, clues_hi, max_scan, chunk, puzzles,
+                                              grids, level, open, index),
+                                  open5_lo, open5_hi, open6_lo, open6_hi, open5, open6),
                        found, scanned);
 }
 

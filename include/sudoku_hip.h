@@ -18,9 +18,11 @@
  *       -> sdk_count_solutions
  *   (no reference counterpart: a batch's verdicts, the technique a board needs,
  *   and inside the search level the number of single-cell backdoors)
- *       -> sdk_classify_batch, sdk_grade_batch, sdk_rate_batch, sdk_subsets_batch, sdk_fish_batch
+ *       -> sdk_classify_batch, sdk_grade_batch, sdk_rate_batch, sdk_subsets_batch, sdk_fish_batch,
+ *          sdk_wings_batch
  *       -> sdk_generate_puzzles, sdk_generate_graded, sdk_generate_rated,
- *          sdk_generate_subsets, sdk_generate_fish, sdk_minimize_level_batch, sdk_generate_level
+ *          sdk_generate_subsets, sdk_generate_fish, sdk_generate_wings, sdk_minimize_level_batch,
+ *          sdk_generate_level
  *   DFS subtree split across ring nodes (NEEDWORK/TASK, DHT_Node.py:491-510,
  *   225-250; utils.py:1-9) -- within one node of GPUs:
  *       -> sdk_frontier_* + sdk_comm_* (RCCL over xGMI)
@@ -59,6 +61,7 @@ extern "C" {
                             /* and sdk_select_rows_dev                                            */
                             /* and sdk_canonical_batch[_dev]                                      */
                             /* and sdk_fish_batch[_dev] and sdk_generate_fish[_dev]               */
+                            /* and sdk_wings_batch[_dev] and sdk_generate_wings[_dev]             */
                             /* (new symbols only: nothing a version-2 caller uses changed)        */
 
 /* return codes */
@@ -371,6 +374,43 @@ int sdk_subsets_batch(sdk_ctx *ctx, const uint8_t *in, uint8_t *out, int8_t *sta
 int sdk_fish_batch(sdk_ctx *ctx, const uint8_t *in, uint8_t *out, int8_t *status, uint8_t *level,
                    uint8_t *open, uint8_t *open4, uint8_t *open5, size_t n, uint64_t node_budget);
 
+/* Wings and simple colouring inside level SDK_GRADE_SEARCH: what do XY-wings, XYZ-wings and simple
+ * colouring leave open?
+ *
+ * R6 = R5 + {W, C} on the grader's candidate sets.  F_6 is its fixpoint.  open6 is the number of open cells
+ * of F_6 for a board of level SDK_GRADE_SEARCH.  For every other board open6 is SDK_WINGS_NONE = 0xFF,
+ * budget hits included.
+ *
+ * W (wings).
+ *   The pivot p is an open cell with 2 or 3 candidates P.
+ *   The pincers q != r are bivalue cells, each sharing a unit with p, with candidate sets Q != R and
+ *   Q & R a single digit z.
+ *   XY-wing:  P == (Q | R) & ~z.  Every cell other than p, q, r that shares a unit with q and with r loses z.
+ *   XYZ-wing: P == Q | R.  Every cell other than p, q, r that shares a unit with p, with q and with r
+ *   loses z.
+ * C (simple colouring, one digit at a time).
+ *   The places of d are the cells that hold candidate d, closed cells included, as in M_d of the fish.
+ *   A link is a unit with exactly two places.
+ *   The links make a graph on the places.  Each connected component with at least one link is two-coloured.
+ *   Wrap: if two places of one colour share a unit, every place of that colour loses d.
+ *   Trap: a place outside the component that shares a unit with a place of each colour loses d.
+ * Both rules remove no digit of a completion.  A premise that further removals break is taken over by
+ * singles, so F_6 is one state whatever the order of application (tests/wings_model.py pins three orders on
+ * data); the stage's order is a W + C pass from F_5, then F_5 again, until a pass changes nothing.
+ *   open6   uint8[n], required.  0..64 for a board of level SDK_GRADE_SEARCH; 0 with open5 > 0: the board
+ *           needs a wing or a colouring, and that is enough.
+ *   open4, open5  uint8[n], nullable: sdk_fish_batch's columns, byte for byte.
+ *   status, out, level, open  exactly sdk_grade_batch's, byte for byte, under every option and budget
+ *           (open nullable).
+ * The call is a grade call with one more stage per slice, in the place of the fish stage (wings_kernel.h:
+ * the fish stage's layout and rounds to F_5, where open5 is taken, then wide rounds).  It changes no option
+ * and leaves SDK_OPT_PROP32_UNDECIDED as a grade call does.  Any n up to 2^31-1; one span under
+ * SDK_OPT_TIMING. */
+#define SDK_WINGS_NONE 0xFFu
+int sdk_wings_batch(sdk_ctx *ctx, const uint8_t *in, uint8_t *out, int8_t *status, uint8_t *level,
+                    uint8_t *open, uint8_t *open4, uint8_t *open5, uint8_t *open6, size_t n,
+                    uint64_t node_budget);
+
 /* Canonical forms for n boards: are two boards the same puzzle under the Sudoku symmetries?
  *
  * A symmetry is a pair (g, rho).  g is a permutation of the cells 0..80 (new cell -> old cell) made of a
@@ -581,6 +621,25 @@ int sdk_generate_fish(sdk_ctx *ctx, uint64_t seed, uint64_t first, size_t n,
                       uint8_t *open4, uint8_t *open5,
                       uint64_t *index, uint64_t *found, uint64_t *scanned);
 
+/* Puzzles of a requested grade, fish count and wings count: sdk_generate_graded with two more conditions.
+ * Candidate k is a hit when it is a hit of sdk_generate_graded(level_mask, clues_lo, clues_hi) and, if its
+ * level is SDK_GRADE_SEARCH, open5_lo <= open5 <= open5_hi and open6_lo <= open6 <= open6_hi
+ * (sdk_wings_batch's counts with no node budget).  Candidates of levels 1..3 are not filtered by the ranges.
+ * open5 = (1, 64), open6 = (0, 0) with level_mask = 1 << SDK_GRADE_SEARCH: the puzzles that need a wing or a
+ * colouring, and for which that is enough.
+ *   open5_lo <= open5_hi <= 64 and open6_lo <= open6_hi <= 64, else SDK_EINVAL;
+ *   open5, open6  uint8[n], nullable: the hits' counts (0xFF for levels 1..3).
+ * Everything else is sdk_generate_graded's.  A round grades with the wings stage; when level_mask lacks
+ * SDK_GRADE_SEARCH the stage is skipped.  With open6 = (0, 64) the rows are sdk_generate_fish's with
+ * open4 = (0, 64); with both ranges (0, 64) the shared outputs are sdk_generate_graded's, byte for byte. */
+int sdk_generate_wings(sdk_ctx *ctx, uint64_t seed, uint64_t first, size_t n,
+                       uint32_t level_mask, uint32_t clues_lo, uint32_t clues_hi,
+                       uint32_t open5_lo, uint32_t open5_hi, uint32_t open6_lo, uint32_t open6_hi,
+                       uint64_t max_scan, uint64_t chunk,
+                       uint8_t *puzzles, uint8_t *grids, uint8_t *level, uint8_t *open,
+                       uint8_t *open5, uint8_t *open6,
+                       uint64_t *index, uint64_t *found, uint64_t *scanned);
+
 /* The worklist step of a resumable lex-first search of a board whose solve hit the
  * budget (distributed_sudoku_solver_amd/search.py; the in-node form of handing a
  * subtree on, DHT_Node.py:491-510): expand n boards -- board i with first-cell mask
@@ -748,6 +807,11 @@ int sdk_subsets_batch_dev(sdk_ctx *ctx, const void *d_in, void *d_out, void *d_s
  * uint8[n] or NULL. */
 int sdk_fish_batch_dev(sdk_ctx *ctx, const void *d_in, void *d_out, void *d_status, void *d_level,
                        void *d_open, void *d_open4, void *d_open5, size_t n, uint64_t node_budget);
+/* as sdk_grade_batch_dev (alignment, d_out may be d_in); d_open6 uint8[n] required, d_open, d_open4 and
+ * d_open5 uint8[n] or NULL. */
+int sdk_wings_batch_dev(sdk_ctx *ctx, const void *d_in, void *d_out, void *d_status, void *d_level,
+                        void *d_open, void *d_open4, void *d_open5, void *d_open6, size_t n,
+                        uint64_t node_budget);
 /* d_in and d_canon 16-byte aligned, else SDK_EINVAL; d_canon may be d_in (exactly).  d_solution, d_gather,
  * d_relabel and d_ties (uint16[n]) or NULL; a d_solution that is not 16-byte aligned only skips the
  * propagation pass, as in sdk_classify_batch_dev. */
@@ -800,6 +864,14 @@ int sdk_generate_fish_dev(sdk_ctx *ctx, uint64_t seed, uint64_t first, size_t n,
                           void *d_puzzles, void *d_grids, void *d_level, void *d_open,
                           void *d_open4, void *d_open5,
                           void *d_index, uint64_t *found, uint64_t *scanned);
+/* as sdk_generate_graded_dev; d_open5 and d_open6 uint8[n] or NULL */
+int sdk_generate_wings_dev(sdk_ctx *ctx, uint64_t seed, uint64_t first, size_t n,
+                           uint32_t level_mask, uint32_t clues_lo, uint32_t clues_hi,
+                           uint32_t open5_lo, uint32_t open5_hi, uint32_t open6_lo, uint32_t open6_hi,
+                           uint64_t max_scan, uint64_t chunk,
+                           void *d_puzzles, void *d_grids, void *d_level, void *d_open,
+                           void *d_open5, void *d_open6,
+                           void *d_index, uint64_t *found, uint64_t *scanned);
 
 /* One round of the selection behind sdk_generate_graded / _rated / _subsets (select_kernel.h), on rows
  * the caller supplies instead of rows the generator and the grader made: the seam through which the
