@@ -41,6 +41,8 @@ SDK_SUBSETS_NONE = 0xFF
 SDK_FISH_NONE = 0xFF
 # sdk_wings_batch: open6 of a board that is not of level SDK_GRADE_SEARCH
 SDK_WINGS_NONE = 0xFF
+# sdk_chains_batch: open7 of a board that is not of level SDK_GRADE_SEARCH
+SDK_CHAINS_NONE = 0xFF
 
 SDK_CHECK_OK = 1
 SDK_CHECK_RAW_NAMEERROR = 2
@@ -150,6 +152,8 @@ SIGNATURES = {
     "sdk_fish_batch_dev": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, ctypes.c_uint64]),
     "sdk_wings_batch": (ctypes.c_int, [_vp] * 9 + [_sz, ctypes.c_uint64]),
     "sdk_wings_batch_dev": (ctypes.c_int, [_vp] * 9 + [_sz, ctypes.c_uint64]),
+    "sdk_chains_batch": (ctypes.c_int, [_vp] * 10 + [_sz, ctypes.c_uint64]),
+    "sdk_chains_batch_dev": (ctypes.c_int, [_vp] * 10 + [_sz, ctypes.c_uint64]),
     # (ctx, in, canon, solution, status, gather, relabel, ties, n, node_budget)
     "sdk_canonical_batch": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, ctypes.c_uint64]),
     "sdk_canonical_batch_dev": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, ctypes.c_uint64]),
@@ -200,6 +204,12 @@ SIGNATURES = {
     "sdk_generate_wings_dev": (ctypes.c_int, [_vp, ctypes.c_uint64, ctypes.c_uint64, _sz] + [ctypes.c_uint32] * 7 +
                                [ctypes.c_uint64, ctypes.c_uint64] + [_vp] * 7 +
                                [ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]),
+    "sdk_generate_chains": (ctypes.c_int, [_vp, ctypes.c_uint64, ctypes.c_uint64, _sz] + [ctypes.c_uint32] * 7 +
+                            [ctypes.c_uint64, ctypes.c_uint64] + [_vp] * 7 +
+                            [ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]),
+    "sdk_generate_chains_dev": (ctypes.c_int, [_vp, ctypes.c_uint64, ctypes.c_uint64, _sz] + [ctypes.c_uint32] * 7 +
+                                [ctypes.c_uint64, ctypes.c_uint64] + [_vp] * 7 +
+                                [ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]),
     "sdk_select_rows_dev": (ctypes.c_int, [_vp, ctypes.POINTER(SelectRows), ctypes.POINTER(ctypes.c_uint64),
                                            ctypes.POINTER(ctypes.c_uint64)]),
     "sdk_frontier_boards_dev": (ctypes.c_int, [_vp, ctypes.POINTER(_vp), ctypes.POINTER(ctypes.c_uint64)]),

@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 
 #include "canon_args.h"
+#include "chains_args.h"
 #include "check_args.h"
 #include "donate_args.h"
 #include "fish_args.h"
@@ -59,6 +60,9 @@ hipError_t launch_fish32(const Fish32Args& a, unsigned grid, hipStream_t stream)
 
 // wings_launch.hip: the same again, with the wide rounds (wings and simple colouring) and three counts
 hipError_t launch_wings32(const Wings32Args& a, unsigned grid, hipStream_t stream);
+
+// chains_launch.hip: the same again, with the chain rounds (X-chains and XY-chains) and four counts
+hipError_t launch_chains32(const Chains32Args& a, unsigned grid, hipStream_t stream);
 
 // canon_launch.hip: one wave per board (grid-stride over the slice)
 hipError_t launch_canon(const CanonArgs& a, unsigned grid, hipStream_t stream);

@@ -198,6 +198,8 @@ struct sdk_ctx {
     DevBuf f5_open4;                     // the fish stage's open4 of a slice where the caller wants none
     DevBuf w6_open6, gg_o6, gg_out_o6;   // sdk_wings_batch, sdk_generate_wings: the same for open6
     DevBuf w6_open5;                     // the wings stage's open5 of a slice where the caller wants none (open4: f5_open4)
+    DevBuf c7_open7, gg_o7, gg_out_o7;   // sdk_chains_batch, sdk_generate_chains: the same for open7
+    DevBuf c7_open6;                     // the chains stage's open6 of a slice where the caller wants none
     DevBuf cn_sol;                 // sdk_canonical_batch_dev without a solution buffer: a slice's completions
     DevBuf cn_gather, cn_relabel, cn_ties;   // sdk_canonical_batch: the host-pointer call's symmetries and tie counts
     DevBuf fr_a, fr_b, prop, bcell, bmask, nchild, offs, fr_status, fr_mask, tsum, fr_ctl;
@@ -316,14 +318,14 @@ struct Piece {
 };
 
 // The copies of a host-pointer call: send() before the launch, fetch() after it (it synchronizes).
-// The (at most ten: sdk_generate_wings) pieces lie in the pinned area (HostBuf) in the order given -- widest element
+// The (at most eleven: sdk_generate_chains) pieces lie in the pinned area (HostBuf) in the order given -- widest element
 // type first, so every slot is aligned for its type; a call too large for the area copies straight
 // from / to the caller's pageable memory.  An error return between send() and the end of fetch()
 // may leave copies from / into the area queued, so the stream is drained first: the next call's
 // memcpy into the area (or a grow that frees it) cannot race them.
 class Staging {
     sdk_ctx* c;
-    Piece p[10];
+    Piece p[11];
     int np = 0;
     bool armed = true;
 
@@ -892,6 +894,10 @@ int launch_classify(sdk_ctx* c, const uint8_t* d_in, uint8_t* d_out, int8_t* d_s
 // of it -- it computes all three counts.  The three columns filled with 0xFF, the same counter cleared, the
 // fish stage's grid.  d_open4 or d_open5 null: the slice's counts go to the context's f5_open4 / w6_open5.
 // Without the pointer nothing of it is enqueued.
+// d_open7 non-null (sdk_chains_batch; chains_kernel.h): the chains stage, where the wings stage sits and in
+// place of it -- it computes all four counts.  The four columns filled with 0xFF, the same counter cleared, the
+// fish stage's grid.  d_open4, d_open5 or d_open6 null: the slice's counts go to the context's f5_open4 /
+// w6_open5 / c7_open6.  Without the pointer nothing of it is enqueued.
 // The columns of a grade call beside out and status, one byte per board: level always, the others nullable.
 struct GradeCols {
     uint8_t *level, *open;
@@ -899,6 +905,7 @@ struct GradeCols {
     uint8_t* open4;             // the subsets stage (sdk_subsets_batch)
     uint8_t* open5 = nullptr;   // the fish stage (sdk_fish_batch), which fills open4 too
     uint8_t* open6 = nullptr;   // the wings stage (sdk_wings_batch), which fills open4 and open5 too
+    uint8_t* open7 = nullptr;   // the chains stage (sdk_chains_batch), which fills open4, open5 and open6 too
 };
 
 int launch_grade(sdk_ctx* c, const uint8_t* d_in, uint8_t* d_out, int8_t* d_status, const GradeCols& cols, size_t n,
@@ -906,7 +913,7 @@ int launch_grade(sdk_ctx* c, const uint8_t* d_in, uint8_t* d_out, int8_t* d_stat
     if (n == 0) return SDK_OK;
     uint8_t *const d_level = cols.level, *const d_open = cols.open, *const d_bd = cols.backdoors,
                    *const d_key = cols.key, *const d_open4 = cols.open4, *const d_open5 = cols.open5,
-                   *const d_open6 = cols.open6;
+                   *const d_open6 = cols.open6, *const d_open7 = cols.open7;
     if ((reinterpret_cast<uintptr_t>(d_in) | reinterpret_cast<uintptr_t>(d_out)) & 15u)
         return fail(SDK_EINVAL, "device boards must be 16-byte aligned");
     if (budget < 0) budget = (int64_t)c->budget;
@@ -915,8 +922,9 @@ int launch_grade(sdk_ctx* c, const uint8_t* d_in, uint8_t* d_out, int8_t* d_stat
     int rc;
     if ((rc = p32_reserve(c, cap)) || (in_place && (rc = ensure(c->gr_in, cap * 81))) ||
         (!d_open && (rc = ensure(c->gr_open, cap))) ||
-        ((d_open5 || d_open6) && !d_open4 && (rc = ensure(c->f5_open4, cap))) ||
-        (d_open6 && !d_open5 && (rc = ensure(c->w6_open5, cap))))
+        ((d_open5 || d_open6 || d_open7) && !d_open4 && (rc = ensure(c->f5_open4, cap))) ||
+        ((d_open6 || d_open7) && !d_open5 && (rc = ensure(c->w6_open5, cap))) ||
+        (d_open7 && !d_open6 && (rc = ensure(c->c7_open6, cap))))
         return rc;
     TimedSpan span(c);
     if ((rc = span.begin())) return rc;
@@ -961,7 +969,26 @@ int launch_grade(sdk_ctx* c, const uint8_t* d_in, uint8_t* d_out, int8_t* d_stat
             if (sdk::launch_rate32(r, grid_for(c, m, 1, 16), c->stream) != hipSuccess)
                 rc = fail(SDK_EHIP, "rate launch failed");
         }
-        if (!rc && d_open6) {
+        if (!rc && d_open7) {
+            sdk::Chains32Args w{};
+            w.in = in;
+            w.level = a.level;
+            w.list = a.p.list;
+            w.n = m;
+            w.next = a.p.heads;
+            w.open4 = d_open4 ? d_open4 + b0 : static_cast<uint8_t*>(c->f5_open4.p);
+            w.open5 = d_open5 ? d_open5 + b0 : static_cast<uint8_t*>(c->w6_open5.p);
+            w.open6 = d_open6 ? d_open6 + b0 : static_cast<uint8_t*>(c->c7_open6.p);
+            w.open7 = d_open7 + b0;
+            HIPCALL(hipMemsetAsync(w.open4, 0xFF, m, c->stream));
+            HIPCALL(hipMemsetAsync(w.open5, 0xFF, m, c->stream));
+            HIPCALL(hipMemsetAsync(w.open6, 0xFF, m, c->stream));
+            HIPCALL(hipMemsetAsync(w.open7, 0xFF, m, c->stream));
+            HIPCALL(hipMemsetAsync(w.next, 0, 4, c->stream));
+            // four waves per SIMD; at most one wave per two listed boards
+            if (sdk::launch_chains32(w, grid_for(c, m, 2, 16), c->stream) != hipSuccess)
+                rc = fail(SDK_EHIP, "chains launch failed");
+        } else if (!rc && d_open6) {
             sdk::Wings32Args w{};
             w.in = in;
             w.level = a.level;
@@ -1255,6 +1282,10 @@ struct GradedCall {
     bool wings = false;
     uint32_t o6_lo = 0, o6_hi = 64;
     uint8_t* open6 = nullptr;
+    // sdk_generate_chains: both o6_lo <= open6 <= o6_hi and o7_lo <= open7 <= o7_hi, and the chains stage
+    bool chains = false;
+    uint32_t o7_lo = 0, o7_hi = 64;
+    uint8_t* open7 = nullptr;
 };
 
 // One round's selection (select_kernel.h): rows [0, m) of caller-supplied buffers -- a round of
@@ -1377,12 +1408,14 @@ int launch_generate_graded(sdk_ctx* c, const GradedCall& g, uint64_t* found, uin
         const bool fish = g.fish && (g.level_mask >> SDK_GRADE_SEARCH & 1u);
         const bool subsets = fish || (g.subsets && (g.level_mask >> SDK_GRADE_SEARCH & 1u));
         const bool wings = g.wings && (g.level_mask >> SDK_GRADE_SEARCH & 1u);
+        const bool chains = g.chains && (g.level_mask >> SDK_GRADE_SEARCH & 1u);
         if ((subsets && (rc = ensure(c->gg_o4, rows))) || ((fish || wings) && (rc = ensure(c->gg_o5, rows))) ||
-            (wings && (rc = ensure(c->gg_o6, rows))))
+            ((wings || chains) && (rc = ensure(c->gg_o6, rows))) || (chains && (rc = ensure(c->gg_o7, rows))))
             return rc;
         uint8_t* o4 = subsets ? static_cast<uint8_t*>(c->gg_o4.p) : nullptr;
         uint8_t* o5 = (fish || wings) ? static_cast<uint8_t*>(c->gg_o5.p) : nullptr;
-        uint8_t* o6 = wings ? static_cast<uint8_t*>(c->gg_o6.p) : nullptr;
+        uint8_t* o6 = (wings || chains) ? static_cast<uint8_t*>(c->gg_o6.p) : nullptr;
+        uint8_t* o7 = chains ? static_cast<uint8_t*>(c->gg_o7.p) : nullptr;
         uint8_t* puz = static_cast<uint8_t*>(c->gg_puz.p);
         uint8_t* grid = static_cast<uint8_t*>(c->gg_grid.p);
         int8_t* st = static_cast<int8_t*>(c->gg_st.p);
@@ -1390,7 +1423,7 @@ int launch_generate_graded(sdk_ctx* c, const GradedCall& g, uint64_t* found, uin
         uint8_t* open = static_cast<uint8_t*>(c->gg_open.p);
         if ((rc = launch_generate_puzzles(c, g.seed, g.first + done, m, puz, grid, st)) ||
             (rc = launch_grade(c, puz, static_cast<uint8_t*>(c->gg_sol.p), static_cast<int8_t*>(c->gg_gst.p),
-                               GradeCols{level, open, bd, key, o4, o5, o6}, m, 0)))
+                               GradeCols{level, open, bd, key, o4, o5, o6, o7}, m, 0)))
             return rc;
         SelectRound r{};
         r.puzzles = puz;
@@ -1439,6 +1472,18 @@ int launch_generate_graded(sdk_ctx* c, const GradedCall& g, uint64_t* found, uin
             r.o4_lo = g.o5_lo;
             r.o4_hi = g.o5_hi;
             r.out_open4 = g.open5;
+        }
+        if (g.chains) {
+            // And once more: a chains call's open7 column and range go through the `backdoors` slot with `key`
+            // null, its open6 and range through the `open4` slot (open4 and open5 are not filtered).
+            r.backdoors = o7;
+            r.bd_lo = g.o7_lo;
+            r.bd_hi = g.o7_hi;
+            r.out_backdoors = g.open7;
+            r.open4 = o6;
+            r.o4_lo = g.o6_lo;
+            r.o4_hi = g.o6_hi;
+            r.out_open4 = g.open6;
         }
         if ((rc = launch_select_round(c, r, d_word))) return rc;
         sdk::SelWord word;
@@ -1495,9 +1540,15 @@ int check_wings_range(uint32_t lo, uint32_t hi) {
     return SDK_OK;
 }
 
+// ... and the open7 range of sdk_generate_chains
+int check_chains_range(uint32_t lo, uint32_t hi) {
+    if (lo > hi || hi > 64) return fail(SDK_EINVAL, "open7 range must be open7_lo <= open7_hi <= 64");
+    return SDK_OK;
+}
+
 uint8_t* u8(void* p) { return static_cast<uint8_t*>(p); }
 
-// sdk_grade_batch, sdk_rate_batch, sdk_subsets_batch, sdk_fish_batch, sdk_wings_batch and their _dev forms, behind each
+// sdk_grade_batch, sdk_rate_batch, sdk_subsets_batch, sdk_fish_batch, sdk_wings_batch, sdk_chains_batch and their _dev forms, behind each
 // one's own test of its required pointers: `cols` holds the columns the entry point has, the others null.  host: the pointers
 // are the caller's arrays, staged through the context's buffers (the same ones whichever family calls);
 // else they are device pointers and the call only enqueues.
@@ -1516,7 +1567,7 @@ int grade_call(sdk_ctx* c, bool host, const void* in, void* out, void* status, c
         (rc = ensure(c->gr_level, n)) || (cols.open && (rc = ensure(c->gr_open, n))) ||
         (cols.backdoors && (rc = ensure(c->rt_bd, n))) || (cols.key && (rc = ensure(c->rt_key, n))) ||
         (cols.open4 && (rc = ensure(c->s4_open4, n))) || (cols.open5 && (rc = ensure(c->f5_open5, n))) ||
-        (cols.open6 && (rc = ensure(c->w6_open6, n))))
+        (cols.open6 && (rc = ensure(c->w6_open6, n))) || (cols.open7 && (rc = ensure(c->c7_open7, n))))
         return rc;
     uint8_t* d_in = u8(c->in.p);
     uint8_t* d_out = u8(c->out.p);
@@ -1524,7 +1575,7 @@ int grade_call(sdk_ctx* c, bool host, const void* in, void* out, void* status, c
     const GradeCols d{u8(c->gr_level.p), cols.open ? u8(c->gr_open.p) : nullptr,
                       cols.backdoors ? u8(c->rt_bd.p) : nullptr, cols.key ? u8(c->rt_key.p) : nullptr,
                       cols.open4 ? u8(c->s4_open4.p) : nullptr, cols.open5 ? u8(c->f5_open5.p) : nullptr,
-                      cols.open6 ? u8(c->w6_open6.p) : nullptr};
+                      cols.open6 ? u8(c->w6_open6.p) : nullptr, cols.open7 ? u8(c->c7_open7.p) : nullptr};
     // a column comes back iff the caller has it (a slot each, present or not)
     auto column = [n](const uint8_t* dev, uint8_t* dst) { return Piece{dst ? n : 0, nullptr, nullptr, dev, dst}; };
     Staging io(c, {{n * 81, in, d_in, d_out, out},
@@ -1535,12 +1586,13 @@ int grade_call(sdk_ctx* c, bool host, const void* in, void* out, void* status, c
                    column(d.key, cols.key),
                    column(d.open4, cols.open4),
                    column(d.open5, cols.open5),
-                   column(d.open6, cols.open6)});
+                   column(d.open6, cols.open6),
+                   column(d.open7, cols.open7)});
     if ((rc = io.send()) || (rc = launch_grade(c, d_in, d_out, d_status, d, n, budget_arg(node_budget)))) return rc;
     return io.fetch();
 }
 
-// sdk_generate_graded, sdk_generate_rated, sdk_generate_subsets, sdk_generate_fish, sdk_generate_wings and their _dev forms:
+// sdk_generate_graded, sdk_generate_rated, sdk_generate_subsets, sdk_generate_fish, sdk_generate_wings, sdk_generate_chains and their _dev forms:
 // `g` is the call with the caller's pointers (its n is set here, from the checked `n`).  host: they are host arrays, and the
 // rows found come back through the context's gg_out_* buffers; else they are device pointers.  The order
 // of the checks is the order of the errors a caller with several bad arguments sees.
@@ -1551,7 +1603,8 @@ int graded_call(sdk_ctx* c, bool host, size_t n, GradedCall g, uint64_t* found, 
         (g.rated && (rc = check_rated_range(g.bd_lo, g.bd_hi))) ||
         (g.subsets && (rc = check_subsets_range(g.o4_lo, g.o4_hi))) ||
         (g.fish && ((rc = check_subsets_range(g.o4_lo, g.o4_hi)) || (rc = check_fish_range(g.o5_lo, g.o5_hi)))) ||
-        (g.wings && ((rc = check_fish_range(g.o5_lo, g.o5_hi)) || (rc = check_wings_range(g.o6_lo, g.o6_hi)))))
+        (g.wings && ((rc = check_fish_range(g.o5_lo, g.o5_hi)) || (rc = check_wings_range(g.o6_lo, g.o6_hi)))) ||
+        (g.chains && ((rc = check_wings_range(g.o6_lo, g.o6_hi)) || (rc = check_chains_range(g.o7_lo, g.o7_hi)))))
         return rc;
     if (!host) {
         if ((reinterpret_cast<uintptr_t>(g.puzzles) | reinterpret_cast<uintptr_t>(g.grids)) & 15u)
@@ -1571,7 +1624,7 @@ int graded_call(sdk_ctx* c, bool host, size_t n, GradedCall g, uint64_t* found, 
                 (g.level && (rc = ensure(c->gg_out_level, rows))) || (g.open && (rc = ensure(c->gg_out_open, rows))) ||
                 (g.backdoors && (rc = ensure(c->gg_out_bd, rows))) || (g.key && (rc = ensure(c->gg_out_key, rows))) ||
                 (g.open4 && (rc = ensure(c->gg_out_o4, rows))) || (g.open5 && (rc = ensure(c->gg_out_o5, rows))) ||
-                (g.open6 && (rc = ensure(c->gg_out_o6, rows))) ||
+                (g.open6 && (rc = ensure(c->gg_out_o6, rows))) || (g.open7 && (rc = ensure(c->gg_out_o7, rows))) ||
                 (g.index && (rc = ensure(c->gg_out_index, rows * 8))))
                 return rc;
             d.puzzles = u8(c->gg_out_puz.p);
@@ -1583,6 +1636,7 @@ int graded_call(sdk_ctx* c, bool host, size_t n, GradedCall g, uint64_t* found, 
             d.open4 = g.open4 ? u8(c->gg_out_o4.p) : nullptr;
             d.open5 = g.open5 ? u8(c->gg_out_o5.p) : nullptr;
             d.open6 = g.open6 ? u8(c->gg_out_o6.p) : nullptr;
+            d.open7 = g.open7 ? u8(c->gg_out_o7.p) : nullptr;
             d.index = g.index ? static_cast<uint64_t*>(c->gg_out_index.p) : nullptr;
         }
         if ((rc = launch_generate_graded(c, d, &f, &s))) return rc;
@@ -1598,7 +1652,8 @@ int graded_call(sdk_ctx* c, bool host, size_t n, GradedCall g, uint64_t* found, 
                            column(d.key, g.key),
                            column(d.open4, g.open4),
                            column(d.open5, g.open5),
-                           column(d.open6, g.open6)});
+                           column(d.open6, g.open6),
+                           column(d.open7, g.open7)});
             if ((rc = io.fetch())) return rc;
         }
     }
@@ -1648,6 +1703,17 @@ GradedCall wings_args(GradedCall g, uint32_t lo5, uint32_t hi5, uint32_t lo6, ui
     g.o6_hi = hi6;
     g.open5 = u8(open5);
     g.open6 = u8(open6);
+    return g;
+}
+
+GradedCall chains_args(GradedCall g, uint32_t lo6, uint32_t hi6, uint32_t lo7, uint32_t hi7, void* open6, void* open7) {
+    g.chains = true;
+    g.o6_lo = lo6;
+    g.o6_hi = hi6;
+    g.o7_lo = lo7;
+    g.o7_hi = hi7;
+    g.open6 = u8(open6);
+    g.open7 = u8(open7);
     return g;
 }
 
@@ -2503,6 +2569,21 @@ int sdk_wings_batch(sdk_ctx* c, const uint8_t* in, uint8_t* out, int8_t* status,
     return grade_call(c, true, in, out, status, {level, open, nullptr, nullptr, open4, open5, open6}, n, node_budget);
 }
 
+int sdk_chains_batch_dev(sdk_ctx* c, const void* d_in, void* d_out, void* d_status, void* d_level, void* d_open,
+                         void* d_open4, void* d_open5, void* d_open6, void* d_open7, size_t n, uint64_t node_budget) {
+    if (!c || (n && (!d_in || !d_out || !d_status || !d_level || !d_open7))) return fail(SDK_EINVAL, "NULL argument");
+    return grade_call(c, false, d_in, d_out, d_status,
+                      {u8(d_level), u8(d_open), nullptr, nullptr, u8(d_open4), u8(d_open5), u8(d_open6), u8(d_open7)},
+                      n, node_budget);
+}
+
+int sdk_chains_batch(sdk_ctx* c, const uint8_t* in, uint8_t* out, int8_t* status, uint8_t* level, uint8_t* open,
+                     uint8_t* open4, uint8_t* open5, uint8_t* open6, uint8_t* open7, size_t n, uint64_t node_budget) {
+    if (!c || (n && (!in || !out || !status || !level || !open7))) return fail(SDK_EINVAL, "NULL argument");
+    return grade_call(c, true, in, out, status, {level, open, nullptr, nullptr, open4, open5, open6, open7}, n,
+                      node_budget);
+}
+
 int sdk_fish_batch_dev(sdk_ctx* c, const void* d_in, void* d_out, void* d_status, void* d_level, void* d_open,
                        void* d_open4, void* d_open5, size_t n, uint64_t node_budget) {
     if (!c || (n && (!d_in || !d_out || !d_status || !d_level || !d_open5))) return fail(SDK_EINVAL, "NULL argument");
@@ -2807,6 +2888,30 @@ int sdk_generate_wings(sdk_ctx* c, uint64_t seed, uint64_t first, size_t n, uint
                        wings_args(graded_args(seed, first, level_mask, clues_lo, clues_hi, max_scan, chunk, puzzles,
                                               grids, level, open, index),
                                   open5_lo, open5_hi, open6_lo, open6_hi, open5, open6),
+                       found, scanned);
+}
+
+int sdk_generate_chains_dev(sdk_ctx* c, uint64_t seed, uint64_t first, size_t n, uint32_t level_mask, uint32_t clues_lo,
+                            uint32_t clues_hi, uint32_t open6_lo, uint32_t open6_hi, uint32_t open7_lo,
+                            uint32_t open7_hi, uint64_t max_scan, uint64_t chunk, void* d_puzzles, void* d_grids,
+                            void* d_level, void* d_open, void* d_open6, void* d_open7, void* d_index, uint64_t* found,
+                            uint64_t* scanned) {
+    return graded_call(c, false, n,
+                       chains_args(graded_args(seed, first, level_mask, clues_lo, clues_hi, max_scan, chunk, d_puzzles,
+                                               d_grids, d_level, d_open, d_index),
+                                   open6_lo, open6_hi, open7_lo, open7_hi, d_open6, d_open7),
+                       found, scanned);
+}
+
+int sdk_generate_chains(sdk_ctx* c, uint64_t seed, uint64_t first, size_t n, uint32_t level_mask, uint32_t clues_lo,
+                        uint32_t clues_hi, uint32_t open6_lo, uint32_t open6_hi, uint32_t open7_lo, uint32_t open7_hi,
+                        uint64_t max_scan, uint64_t chunk, uint8_t* puzzles, uint8_t* grids, uint8_t* level,
+                        uint8_t* open, uint8_t* open6, uint8_t* open7, uint64_t* index, uint64_t* found,
+                        uint64_t* scanned) {
+    return graded_call(c, true, n,
+                       chains_args(graded_args(seed, first, level_mask, clues_lo, clues_hi, max_scan, chunk, puzzles,
+                                               grids, level, open, index),
+                                   open6_lo, open6_hi, open7_lo, open7_hi, open6, open7),
                        found, scanned);
 }
 

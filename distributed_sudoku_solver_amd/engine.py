@@ -406,6 +406,27 @@ class SudokuEngine:
                 "sdk_wings_batch")
         return status, level, open_, open4, open5, open6, out
 
+    def chains_batch(self, boards, budget=None):
+        """uint8[n,81] -> (status int8[n], level uint8[n], open uint8[n], open4 uint8[n], open5 uint8[n],
+        open6 uint8[n], open7 uint8[n], out uint8[n,81]): wings_batch, and for every level-4 board the number
+        of cells still open once X-chains and XY-chains join the wings and simple colouring
+        (sdk_chains_batch).  open6 > 0 and open7 == 0: the board needs a chain, and a chain is enough; open7
+        is SDK_CHAINS_NONE = 0xFF for every board of another level.  status, level, open and out are exactly
+        grade_batch's, open4, open5 and open6 are wings_batch's.  Not sharded by MultiDeviceEngine or
+        ShardedBatch: it runs on this engine's device."""
+        boards = np.ascontiguousarray(boards, dtype=np.uint8).reshape(-1, 81)
+        n = boards.shape[0]
+        if budget is not None and not 0 <= int(budget) < (1 << 63):
+            raise ValueError("budget must be 0 (unlimited) or a positive node count")
+        out = np.empty_like(boards)
+        status = np.empty(n, dtype=np.int8)
+        level, open_, open4, open5, open6, open7 = (np.empty(n, dtype=np.uint8) for _ in range(6))
+        L.check(self.lib.sdk_chains_batch(self.ctx, _ptr(boards), _ptr(out), _ptr(status), _ptr(level), _ptr(open_),
+                                          _ptr(open4), _ptr(open5), _ptr(open6), _ptr(open7), n,
+                                          L.SDK_BUDGET_CONTEXT if budget is None else int(budget)),
+                "sdk_chains_batch")
+        return status, level, open_, open4, open5, open6, open7, out
+
     def canonical_batch(self, boards, budget=None):
         """uint8[n,81] -> (status int8[n], canon uint8[n,81], solution uint8[n,81], gather uint8[n,81],
         relabel uint8[n,10], ties uint16[n]): the canonical form of each board under the Sudoku
@@ -544,7 +565,8 @@ class SudokuEngine:
     def _graded_args(n, levels, seed, lo, clues, max_scan, chunk, band=None, band2=None):
         """The arguments of sdk_generate_graded from generate_graded's (ValueError for a bad one); band =
         (name, range) adds the (lo, hi) of sdk_generate_rated's backdoors or sdk_generate_subsets' open4,
-        band2 a second pair behind it (sdk_generate_fish's open5, sdk_generate_wings' open6)."""
+        band2 a second pair behind it (sdk_generate_fish's open5, sdk_generate_wings' open6,
+        sdk_generate_chains' open7)."""
         n, seed, lo = SudokuEngine._stream_rows(n, seed, lo)
         if n >= 1 << 31:
             raise ValueError("n must be below 2^31")
@@ -654,6 +676,17 @@ class SudokuEngine:
         generate_graded."""
         args = self._graded_args(n, levels, seed, lo, clues, max_scan, chunk, ("open5", open5), ("open6", open6))
         return self._generate_selected("wings", args, 2)
+
+    def generate_chains(self, n, levels=(1, 2, 3, 4), seed=synth.DEFAULT_SEED + 3, lo=0, clues=None, open6=None,
+                        open7=None, max_scan=1 << 26, chunk=0):
+        """generate_graded with a wings and a chains filter (sdk_generate_chains): a level-4 puzzle is kept
+        only when its chains_batch counts lie in open6 = (lo, hi) and open7 = (lo, hi) (None: 0..64); puzzles
+        of levels 1..3 are not filtered by them.  levels=(4,), open6=(1, 64), open7=(0, 0): the puzzles that
+        need a chain, and for which a chain is enough.  Returns generate_graded's tuple with the counts after
+        open: (puzzles, solutions, level, open, open6 uint8[found], open7 uint8[found], index, scanned); both
+        are 0xFF for the puzzles of levels 1..3.  Not sharded by MultiDeviceEngine, like generate_graded."""
+        args = self._graded_args(n, levels, seed, lo, clues, max_scan, chunk, ("open6", open6), ("open7", open7))
+        return self._generate_selected("chains", args, 2)
 
     def expand(self, boards, masks=None, target=64):
         """Lex-ordered frontier below `boards` (sdk_expand_boards): uint8[k,81], children in the
@@ -873,6 +906,17 @@ class SudokuEngine:
                                              L.SDK_BUDGET_CONTEXT if budget is None else int(budget)),
                 "sdk_wings_batch_dev")
 
+    def chains_batch_dev(self, d_in, d_out, d_status, d_level, d_open7, n, d_open=None, d_open4=None, d_open5=None,
+                         d_open6=None, budget=None):
+        """chains_batch on device buffers: as grade_batch_dev (d_in and d_out 16-byte aligned, d_out may be
+        d_in), d_open7 required, d_open, d_open4, d_open5 and d_open6 optional."""
+        L.check(self.lib.sdk_chains_batch_dev(self.ctx, d_in.ptr, d_out.ptr, d_status.ptr, d_level.ptr,
+                                              d_open.ptr if d_open else None, d_open4.ptr if d_open4 else None,
+                                              d_open5.ptr if d_open5 else None, d_open6.ptr if d_open6 else None,
+                                              d_open7.ptr if d_open7 else None, int(n),
+                                              L.SDK_BUDGET_CONTEXT if budget is None else int(budget)),
+                "sdk_chains_batch_dev")
+
     def canonical_batch_dev(self, d_in, d_canon, d_status, n, d_solution=None, d_gather=None, d_relabel=None,
                             d_ties=None, budget=None):
         """canonical_batch on device buffers: d_in and d_canon 16-byte aligned (d_canon may be d_in);
@@ -948,6 +992,14 @@ class SudokuEngine:
         """generate_wings into device buffers of n rows, as generate_graded_dev: -> (found, scanned)."""
         args = self._graded_args(n, levels, seed, lo, clues, max_scan, chunk, ("open5", open5), ("open6", open6))
         return self._generate_selected_dev("wings", args, d_puzzles, d_grids, (d_level, d_open, d_open5, d_open6),
+                                           d_index)
+
+    def generate_chains_dev(self, d_puzzles, d_grids, n, levels=(1, 2, 3, 4), seed=synth.DEFAULT_SEED + 3, lo=0,
+                            clues=None, open6=None, open7=None, max_scan=1 << 26, chunk=0, d_level=None, d_open=None,
+                            d_open6=None, d_open7=None, d_index=None):
+        """generate_chains into device buffers of n rows, as generate_graded_dev: -> (found, scanned)."""
+        args = self._graded_args(n, levels, seed, lo, clues, max_scan, chunk, ("open6", open6), ("open7", open7))
+        return self._generate_selected_dev("chains", args, d_puzzles, d_grids, (d_level, d_open, d_open6, d_open7),
                                            d_index)
 
     def select_rows_dev(self, rows):

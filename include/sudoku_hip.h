@@ -19,10 +19,10 @@
  *   (no reference counterpart: a batch's verdicts, the technique a board needs,
  *   and inside the search level the number of single-cell backdoors)
  *       -> sdk_classify_batch, sdk_grade_batch, sdk_rate_batch, sdk_subsets_batch, sdk_fish_batch,
- *          sdk_wings_batch
+ *          sdk_wings_batch, sdk_chains_batch
  *       -> sdk_generate_puzzles, sdk_generate_graded, sdk_generate_rated,
- *          sdk_generate_subsets, sdk_generate_fish, sdk_generate_wings, sdk_minimize_level_batch,
- *          sdk_generate_level
+ *          sdk_generate_subsets, sdk_generate_fish, sdk_generate_wings, sdk_generate_chains,
+ *          sdk_minimize_level_batch, sdk_generate_level
  *   DFS subtree split across ring nodes (NEEDWORK/TASK, DHT_Node.py:491-510,
  *   225-250; utils.py:1-9) -- within one node of GPUs:
  *       -> sdk_frontier_* + sdk_comm_* (RCCL over xGMI)
@@ -62,6 +62,7 @@ extern "C" {
                             /* and sdk_canonical_batch[_dev]                                      */
                             /* and sdk_fish_batch[_dev] and sdk_generate_fish[_dev]               */
                             /* and sdk_wings_batch[_dev] and sdk_generate_wings[_dev]             */
+                            /* and sdk_chains_batch[_dev] and sdk_generate_chains[_dev]           */
                             /* (new symbols only: nothing a version-2 caller uses changed)        */
 
 /* return codes */
@@ -411,6 +412,44 @@ int sdk_wings_batch(sdk_ctx *ctx, const uint8_t *in, uint8_t *out, int8_t *statu
                     uint8_t *open, uint8_t *open4, uint8_t *open5, uint8_t *open6, size_t n,
                     uint64_t node_budget);
 
+/* Chains inside level SDK_GRADE_SEARCH: what do X-chains and XY-chains leave open?
+ *
+ * R7 = R6 + {X, Y} on the grader's candidate sets.  F_7 is its fixpoint.  open7 is the number of open cells
+ * of F_7 for a board of level SDK_GRADE_SEARCH.  For every other board open7 is SDK_CHAINS_NONE = 0xFF,
+ * budget hits included.
+ *
+ * X (X-chains, one digit d at a time).
+ *   The places of d are the cells that hold candidate d, closed cells included, as in M_d of the fish and the
+ *   colouring's places.  A link is a unit with exactly two places.
+ *   For every open place s: ON starts as the other ends of the links through s.  Until ON stops growing, OFF
+ *   is the places that share a unit with a cell of ON, and every link with exactly one end in OFF puts its
+ *   other end into ON; s itself is never put into ON.
+ *   For every t in ON either s or t holds d: every open cell that shares a unit with s and with t loses d.
+ *   Skyscrapers, two-string kites, turbot fish and the colour trap are its short cases.
+ * Y (XY-chains).
+ *   For every bivalue cell s and each of its two digits z: a state (c, v) means "c is v"; the start state is
+ *   (s, the other digit of s); from (c, v) the chain goes to every bivalue cell c2 != s that shares a unit
+ *   with c and holds v, in the state (c2, the other digit of c2).
+ *   For every reached state (c, z) with c != s either s or c holds z: every open cell that shares a unit with
+ *   s and with c loses z.  XY-wings are the length-three case; remote pairs are included.
+ * Both rules remove no digit of a completion.  A premise that further removals break becomes a single, so F_7
+ * is one state whatever the order of application (tests/chains_model.py pins three orders on data); the
+ * stage's order is an X + Y pass from F_6, both from one snapshot, then F_6 again, until a pass changes
+ * nothing.  No chain removal touches a board before its open4, open5 and open6 are stored.
+ *   open7   uint8[n], required.  0..64 for a board of level SDK_GRADE_SEARCH; 0 with open6 > 0: the board
+ *           needs a chain, and a chain is enough.
+ *   open4, open5, open6  uint8[n], nullable: sdk_wings_batch's columns, byte for byte.
+ *   status, out, level, open  exactly sdk_grade_batch's, byte for byte, under every option and budget
+ *           (open nullable).
+ * The call is a grade call with one more stage per slice, in the place of the wings stage (chains_kernel.h:
+ * the wings stage's layout and rounds to F_6, where open6 is taken, then chain rounds).  It changes no option
+ * and leaves SDK_OPT_PROP32_UNDECIDED as a grade call does.  Any n up to 2^31-1; one span under
+ * SDK_OPT_TIMING. */
+#define SDK_CHAINS_NONE 0xFFu
+int sdk_chains_batch(sdk_ctx *ctx, const uint8_t *in, uint8_t *out, int8_t *status, uint8_t *level,
+                     uint8_t *open, uint8_t *open4, uint8_t *open5, uint8_t *open6, uint8_t *open7, size_t n,
+                     uint64_t node_budget);
+
 /* Canonical forms for n boards: are two boards the same puzzle under the Sudoku symmetries?
  *
  * A symmetry is a pair (g, rho).  g is a permutation of the cells 0..80 (new cell -> old cell) made of a
@@ -640,6 +679,25 @@ int sdk_generate_wings(sdk_ctx *ctx, uint64_t seed, uint64_t first, size_t n,
                        uint8_t *open5, uint8_t *open6,
                        uint64_t *index, uint64_t *found, uint64_t *scanned);
 
+/* Puzzles of a requested grade, wings count and chains count: sdk_generate_graded with two more conditions.
+ * Candidate k is a hit when it is a hit of sdk_generate_graded(level_mask, clues_lo, clues_hi) and, if its
+ * level is SDK_GRADE_SEARCH, open6_lo <= open6 <= open6_hi and open7_lo <= open7 <= open7_hi
+ * (sdk_chains_batch's counts with no node budget).  Candidates of levels 1..3 are not filtered by the ranges.
+ * open6 = (1, 64), open7 = (0, 0) with level_mask = 1 << SDK_GRADE_SEARCH: the puzzles that need a chain, and
+ * for which a chain is enough.
+ *   open6_lo <= open6_hi <= 64 and open7_lo <= open7_hi <= 64, else SDK_EINVAL;
+ *   open6, open7  uint8[n], nullable: the hits' counts (0xFF for levels 1..3).
+ * Everything else is sdk_generate_graded's.  A round grades with the chains stage; when level_mask lacks
+ * SDK_GRADE_SEARCH the stage is skipped.  With open7 = (0, 64) the rows are sdk_generate_wings' with
+ * open5 = (0, 64); with both ranges (0, 64) the shared outputs are sdk_generate_graded's, byte for byte. */
+int sdk_generate_chains(sdk_ctx *ctx, uint64_t seed, uint64_t first, size_t n,
+                        uint32_t level_mask, uint32_t clues_lo, uint32_t clues_hi,
+                        uint32_t open6_lo, uint32_t open6_hi, uint32_t open7_lo, uint32_t open7_hi,
+                        uint64_t max_scan, uint64_t chunk,
+                        uint8_t *puzzles, uint8_t *grids, uint8_t *level, uint8_t *open,
+                        uint8_t *open6, uint8_t *open7,
+                        uint64_t *index, uint64_t *found, uint64_t *scanned);
+
 /* The worklist step of a resumable lex-first search of a board whose solve hit the
  * budget (distributed_sudoku_solver_amd/search.py; the in-node form of handing a
  * subtree on, DHT_Node.py:491-510): expand n boards -- board i with first-cell mask
@@ -812,6 +870,11 @@ int sdk_fish_batch_dev(sdk_ctx *ctx, const void *d_in, void *d_out, void *d_stat
 int sdk_wings_batch_dev(sdk_ctx *ctx, const void *d_in, void *d_out, void *d_status, void *d_level,
                         void *d_open, void *d_open4, void *d_open5, void *d_open6, size_t n,
                         uint64_t node_budget);
+/* as sdk_grade_batch_dev (alignment, d_out may be d_in); d_open7 uint8[n] required, d_open, d_open4,
+ * d_open5 and d_open6 uint8[n] or NULL. */
+int sdk_chains_batch_dev(sdk_ctx *ctx, const void *d_in, void *d_out, void *d_status, void *d_level,
+                         void *d_open, void *d_open4, void *d_open5, void *d_open6, void *d_open7, size_t n,
+                         uint64_t node_budget);
 /* d_in and d_canon 16-byte aligned, else SDK_EINVAL; d_canon may be d_in (exactly).  d_solution, d_gather,
  * d_relabel and d_ties (uint16[n]) or NULL; a d_solution that is not 16-byte aligned only skips the
  * propagation pass, as in sdk_classify_batch_dev. */
@@ -872,6 +935,14 @@ int sdk_generate_wings_dev(sdk_ctx *ctx, uint64_t seed, uint64_t first, size_t n
                            void *d_puzzles, void *d_grids, void *d_level, void *d_open,
                            void *d_open5, void *d_open6,
                            void *d_index, uint64_t *found, uint64_t *scanned);
+/* as sdk_generate_graded_dev; d_open6 and d_open7 uint8[n] or NULL */
+int sdk_generate_chains_dev(sdk_ctx *ctx, uint64_t seed, uint64_t first, size_t n,
+                            uint32_t level_mask, uint32_t clues_lo, uint32_t clues_hi,
+                            uint32_t open6_lo, uint32_t open6_hi, uint32_t open7_lo, uint32_t open7_hi,
+                            uint64_t max_scan, uint64_t chunk,
+                            void *d_puzzles, void *d_grids, void *d_level, void *d_open,
+                            void *d_open6, void *d_open7,
+                            void *d_index, uint64_t *found, uint64_t *scanned);
 
 /* One round of the selection behind sdk_generate_graded / _rated / _subsets (select_kernel.h), on rows
  * the caller supplies instead of rows the generator and the grader made: the seam through which the
